@@ -2,6 +2,7 @@
 """Headline benchmark: focal-stacks/sec of the depth-from-focus forward on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision bf16x3|fp16|bf16]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (DFF_net.forward, reference DEN.py:74-127, through
 libdffw.so) over one batch of synthetic 10-slice 3x256x256 focal stacks per GPU — BASELINE.json's
@@ -15,7 +16,17 @@ all-gather inside the timed step (its bus GB/s is reported under "allgather").
 `--workload e2e` runs BASELINE.json's config 5 instead (not the default line): the End_to_End variant —
 alignment network + FOV warp + DFF_net (End_to_End/End_to_End.py) — on 10-slice 480x640 stacks, batch 8.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` is stacks/s over the K
+steps, `ms_per_step` the milliseconds of one of them.  `--dump-outputs DIR` writes what the last timed step returned
+(mid_out, pred1, pred2, pred3, and `aligned` for e2e, `pred3_all_ranks` for N > 1) as DIR/<name>.npy in float32,
+64 MB at most in all: each array gets an equal share, and one larger than its share is written as a fixed sample
+(seed 0, flat indices in ascending order).  Inputs and weights are seeded, so the same arguments give the same inputs.
+
+Everything else the benchmark measures runs only with `--full`, after the timed steps (`--no-roofline`,
+`--no-other-configs`, `--no-cpu-baseline`, `--sustain-seconds 0` drop single parts of it):
+  sustained     the step repeated until --sustain-seconds have been timed (single GPU)
+  allgather     the step's one collective timed on its own (N > 1)
+  configs       short runs of BASELINE.json configs 1, 2 and 5 (default shape, single GPU)
   roofline      the dominant kernel (by summed time) of one profiled forward: algorithmic FLOPs per
                 launch / HIP-event duration per launch against the dense MFMA peak of the
                 instruction type issued (2.5 PFLOP/s bf16/f16; split-bf16 issues 3 MFMAs per
@@ -41,6 +52,22 @@ from dffinthewild_amd import graph, synth  # noqa: E402
 GFLOP_PER_STACK = 61.317          # 10x256x256, 2*MAC over the 70 convs
 PEAK_MFMA_TFLOPS = 2500.0         # dense bf16/f16 MFMA, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+OUT_NAMES = ("mid_out", "pred1", "pred2", "pred3", "aligned")
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32, DUMP_BYTES at most in all.  An array larger than its equal share
+    is written as the elements at a fixed set of flat indices (seed 0, ascending), so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    k = (DUMP_BYTES // len(arrays) - 4096) // 4        # elements per array (4096: room for the .npy header)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > k:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def build_model(precision, device, workload="depth"):
@@ -439,11 +466,20 @@ def main():
     ap.add_argument("--input", choices=("fp32", "u8"), default="fp32",
                     help="fp32: the reference's tensor contract (B,3,N,H,W) float32 (default, the headline); u8: the raw uint8 "
                          "(B,N,H,W,3) stack a loader holds before /127.5-1, normalised inside the stem kernel (Network.forward_raw)")
-    ap.add_argument("--dump-layers", default=None, help="write the per-launch profile table to this file")
+    ap.add_argument("--dump-layers", default=None, help="write the per-launch profile table to this file (needs --full)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs 1, 2 and 5 (`configs` key)")
     ap.add_argument("--sustain-seconds", type=float, default=4.0,
                     help="after the K timed steps, keep stepping until this many seconds have been timed in total and report it as `sustained`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, 64 MB at most in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the sustained region, the all-gather, BASELINE configs 1, 2 and 5, "
+                         "the roofline of one profiled forward and the CPU baseline with parity (off: the headline only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs --full (the table comes from the profiled forward)")
 
     rank, local_rank, world = ddist.env_world()
     if world == 1 and args.gpus > 1:
@@ -509,10 +545,15 @@ def main():
         elapsed = float(t.item())
     stacks = world * B * args.steps
     value = stacks / elapsed
+    if args.dump_outputs and rank == 0:
+        arrays = dict(zip(OUT_NAMES, outs))
+        if world > 1:
+            arrays["pred3_all_ranks"] = gathered
+        dump_outputs(args.dump_outputs, arrays)
     # the K steps of the contract are `value`; the same step repeated until >= --sustain-seconds have been timed (single GPU:
     # the default K = 10 is a 0.1 s region) is reported beside it as `sustained`
     sustained = None
-    if world == 1 and args.sustain_seconds > 0 and elapsed < args.sustain_seconds:
+    if args.full and world == 1 and args.sustain_seconds > 0 and elapsed < args.sustain_seconds:
         more = int((args.sustain_seconds - elapsed) / (elapsed / args.steps)) + 1
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
@@ -523,7 +564,7 @@ def main():
         sustained = {"steps_effective": args.steps + more, "seconds": round(elapsed + el2, 3),
                      "value": round(B * (args.steps + more) / (elapsed + el2), 2), "unit": "stacks/s",
                      "ms_per_step": round((elapsed + el2) / (args.steps + more) * 1e3, 3)}
-    allgather = measure_allgather(outs[3], world) if world > 1 else None
+    allgather = measure_allgather(outs[3], world) if args.full and world > 1 else None
 
     result = None
     if rank == 0:
@@ -553,7 +594,7 @@ def main():
             result["allgather"] = allgather
         if sustained:
             result["sustained"] = sustained
-    if rank == 0 and not args.no_roofline and raw_u8 is None:
+    if rank == 0 and args.full and not args.no_roofline and raw_u8 is None:
         roof, per_kernel, rows = roofline_from_profile(model, inputs, device, args.precision)
         result["roofline"] = roof
         result["kernels"] = per_kernel
@@ -562,12 +603,12 @@ def main():
                 f.write("kernel\tlayer\tgflop\talg_MB\tms\ttflops\talg_GBs\n")
                 for k, l, fl, by, ms in rows:
                     f.write(f"{k}\t{l}\t{fl/1e9:.3f}\t{by/1e6:.2f}\t{ms:.4f}\t{fl/(ms*1e-3)/1e12 if ms else 0:.2f}\t{by/(ms*1e-3)/1e9 if ms else 0:.1f}\n")
-    if rank == 0 and world == 1 and not args.no_other_configs and not e2e and raw_u8 is None and (B, N, S) == (32, 10, 256):
+    if rank == 0 and args.full and world == 1 and not args.no_other_configs and not e2e and raw_u8 is None and (B, N, S) == (32, 10, 256):
         try:
             result["configs"] = other_configs(model, args.precision, device)
         except Exception as exc:   # noqa: BLE001 -- the extra runs must not cost the headline line
             result["configs"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and raw_u8 is None and (e2e or (N, S) == (10, 256)):
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and raw_u8 is None and (e2e or (N, S) == (10, 256)):
         from oracle import cpu_ref
         base, ref = cpu_baseline_e2e(sd, args.cpu_seconds, Hh, Ww) if e2e else cpu_baseline(sd, args.cpu_seconds)
         result["cpu_baseline"] = base

@@ -14,7 +14,7 @@ for spec in args:
 vals = {n: [] for n, _ in variants}
 for r in range(reps):
     for name, env in variants:
-        out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-other-configs", "--no-roofline", "--sustain-seconds", secs, "--steps", "10", "--warmup", "5"],
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-roofline", "--sustain-seconds", secs, "--steps", "10", "--warmup", "5"],
                              env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode()
         d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
         vals[name].append(d["sustained"]["ms_per_step"])

@@ -13,7 +13,7 @@ for r in range(reps):
     for name, env in variants:
         with tempfile.NamedTemporaryFile(suffix=".tsv", delete=False) as f:
             path = f.name
-        subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0", "--steps", "3", "--warmup", "2",
+        subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0", "--steps", "3", "--warmup", "2",
                         "--dump-layers", path], env=dict(os.environ, **env), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
         rows = list(csv.reader(open(path), delimiter="\t"))[1:]
         os.unlink(path)

@@ -2459,6 +2459,9 @@ int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin,
                              + 8 * opix * ((Cout + 15) / 16 * 16) * 4 + 4096;   // + split-K partial sums (up to 8 splits)
     char *ws = nullptr;
     HIPCHK(hipMalloc((void **)&ws, ws_bytes));
+    // poisoned: 0xFF bytes are NaN in fp32, bf16 and fp16, so an output element no kernel stores, or a workspace value read before it is
+    // written, shows as NaN instead of as whatever the previous call left in a recycled block (the op path is test-only, not the forward's)
+    HIPCHK(hipMemsetAsync(ws, 0xFF, ws_bytes, s));
     Run r(&eng, s, false, ws, ws_bytes);
     Act res;
     ConvOpt o;
@@ -2508,6 +2511,7 @@ int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int
     const int64_t nin = (int64_t)B * N * H * W * parts * C, nout = (int64_t)B * N * (H / k) * (W / k) * parts * C;
     HIPCHK(hipMalloc((void **)&a, nin * 2));
     HIPCHK(hipMalloc((void **)&b, nout * 2));
+    HIPCHK(hipMemsetAsync(b, 0xFF, nout * 2, s));   // poisoned (NaN in every format): an output the pool kernel does not store shows
     int rc = DFFW_OK;
     hipError_t h = launch_from_ncdhw(precision, x, a, B, C, N, H, W, s);
     if (h == hipSuccess) h = launch_pool(precision, mode, k, a, b, B, N, H, W, C, s);

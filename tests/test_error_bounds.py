@@ -1,0 +1,257 @@
+"""CPU self-test of oracle/error_bounds.py: the op path's arithmetic emulated in torch (split-bf16 with three products, fp16 and bf16
+with one, fp32 accumulation, 16-bit storage) must stay within the per-element bound with room to spare, and the local faults a kernel
+or a fragment writer can make -- a strip computed from hi halves only, one missed product, one element off by 1e-3 S, a missed tap at
+a corner, one stray lo fragment -- must exceed it by 4x or more, although the first three stay under the op tests' relative-L2 gate.
+No GPU: this pins what the bound can see."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import error_bounds as eb
+
+REL_GATE = {"bf16x3": 5e-5, "fp16": 3e-3, "bf16": 2e-2}
+
+
+def rel(a, b):
+    a, b = a.double().reshape(-1), b.double().reshape(-1)
+    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def _round(v, fmt):
+    return v.to(fmt).float()
+
+
+def split(v, prec):
+    """(hi, lo) of an fp32 tensor in the op's storage / operand format (lo = 0 for the one-product formats)."""
+    if prec == "bf16x3":
+        hi = _round(v, torch.bfloat16)
+        return hi, _round(v - hi, torch.bfloat16)
+    hi = _round(v, torch.float16 if prec == "fp16" else torch.bfloat16)
+    return hi, torch.zeros_like(hi)
+
+
+def store(v, prec):
+    hi, lo = split(v, prec)
+    return hi + lo
+
+
+def _conv32(x, w, geo):
+    if geo["transposed"]:
+        return F.conv_transpose3d(x, w, None, geo["stride"], geo["pad"], (0, 1, 1))
+    return F.conv3d(x, w, None, geo["stride"], geo["pad"], geo["dilation"])
+
+
+def fold(w, bn, transposed):
+    """BN folded into the weights in fp32, as the packer does: (w * s_c, t_c)."""
+    s, t = eb.fold_bn(bn, w.shape[1] if transposed else w.shape[0])
+    s, t = s.float(), t.float()
+    ws = w * (s.reshape(1, -1, 1, 1, 1) if transposed else s.reshape(-1, 1, 1, 1, 1))
+    return ws, t
+
+
+def emulate(x, w, geo, bn, residual, relu, prec, hi_only=None):
+    """The op's result: operands in the storage format, fp32 accumulation of hi*hi + hi*lo + lo*hi (one product for fp16 / bf16),
+    shift, residual (stored), ReLU, stored result.  ``hi_only`` (mask over the output) replaces the cross products by zero there."""
+    ws, t = fold(w, bn, geo["transposed"])
+    xh, xl = split(x, prec)
+    wh, wl = split(ws, prec)
+    acc = _conv32(xh, wh, geo)
+    if prec == "bf16x3":
+        cross = _conv32(xh, wl, geo) + _conv32(xl, wh, geo)
+        acc = acc + (cross if hi_only is None else cross * (~hi_only))
+    y = acc + t.reshape(1, -1, 1, 1, 1)
+    if residual is not None:
+        r = store(residual, prec)
+        y = (F.relu(y) + r) if relu == 2 else (y + r)
+        if relu == 1:
+            y = F.relu(y)
+    elif relu:
+        y = F.relu(y)
+    return store(y, prec)
+
+
+def geo(stride=1, pad=0, dilation=1, transposed=False):
+    return dict(stride=stride, pad=pad, dilation=dilation, transposed=transposed)
+
+
+# name, Cin, Cout, kernel, geometry, (B, N, H, W), residual, relu
+CASES = [
+    ("c3_s1_32_32", 32, 32, (3, 3, 3), geo(1, 1), (1, 4, 16, 24), True, 1),
+    ("c3_s2_16_32", 16, 32, (3, 3, 3), geo((1, 2, 2), 1), (1, 3, 16, 32), False, 1),
+    ("t3_32_16", 32, 16, (3, 3, 3), geo((1, 2, 2), 1, transposed=True), (1, 3, 8, 12), True, 2),
+    ("stem_1x9x9_dil2", 3, 8, (1, 9, 9), geo(1, (0, 8, 8), (1, 2, 2)), (1, 2, 16, 24), False, 1),
+    ("p1_24_16", 24, 16, (1, 1, 1), geo(), (1, 3, 8, 8), True, 0),
+    ("a3x1x1_16_16", 16, 16, (3, 1, 1), geo(1, (1, 0, 0)), (1, 5, 8, 8), False, 1),
+    ("c3_192_128", 192, 128, (3, 3, 3), geo(1, 1), (1, 3, 6, 6), False, 1),
+]
+
+
+def make_case(case, regime, seed=0):
+    name, cin, cout, k, g, (B, N, H, W), residual, relu = case
+    x = eb.regime_input(regime, (B, cin, N, H, W), seed)
+    wshape = (cin, cout, *k) if g["transposed"] else (cout, cin, *k)
+    K = cin * k[0] * k[1] * k[2] // (4 if g["transposed"] else 1)
+    gen = torch.Generator().manual_seed(seed + 1)
+    w = (torch.rand(*wshape, generator=gen) * 2 - 1) * (2.0 / K) ** 0.5 * 1.7
+    conv_mean = 3.0 * float(w.sum() / cout) if regime == "offset" else 0.0
+    bn = eb.bn_regime(regime, cout, seed + 2, conv_mean=conv_mean)
+    r64 = eb.conv_ref64(x, w, stride=g["stride"], pad=g["pad"], dilation=g["dilation"], transposed=g["transposed"], bn=bn)
+    res = None
+    if residual and regime != "impulse":
+        res = (torch.rand(*r64.ref.shape, generator=gen) * 2 - 1)
+    return x, w, bn, res, relu
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
+@pytest.mark.parametrize("regime", ["plain"] + list(eb.REGIMES))
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c[0])
+def test_emulated_arithmetic_within_bound(case, regime, prec):
+    """Every emulated result within half the bound (the derivation's worst ratio is ~0.25)."""
+    _, _, _, _, g, _, _, _ = case
+    x, w, bn, res, relu = make_case(case, regime)
+    r = eb.conv_ref64(x, w, stride=g["stride"], pad=g["pad"], dilation=g["dilation"], transposed=g["transposed"], bn=bn,
+                      residual=res, relu=relu)
+    got = emulate(x, w, g, bn, res, relu, prec)
+    assert torch.isfinite(got).all()
+    assert float(r.ref.abs().max()) < 1e4           # inside fp16 range, with room
+    worst = eb.check_elementwise(got, r, prec)
+    assert worst <= 0.5, (case[0], regime, prec, worst)
+    if regime == "impulse":                          # the footprint only: exact zeros elsewhere
+        assert torch.equal(got[r.D == 0], torch.zeros_like(got[r.D == 0]))
+
+
+def test_bound_sees_the_bf16x3_depth_limit():
+    """One missed product at K = 5184 must stay visible: alpha(bf16x3) <= 2^-14."""
+    assert eb.ALPHA["bf16x3"] <= 2.0 ** -14
+
+
+# ---- fault injection: the 32 -> 32 3x3x3 conv of the issue's table, split-bf16 -------------------------------------------------
+FAULT_SHAPE = (1, 32, 10, 64, 64)
+
+
+@pytest.fixture(scope="module")
+def fault_case():
+    g = geo(1, 1)
+    gen = torch.Generator().manual_seed(7)
+    x = torch.rand(*FAULT_SHAPE, generator=gen) * 2 - 1
+    w = (torch.rand(32, 32, 3, 3, 3, generator=gen) * 2 - 1) * (2.0 / 864) ** 0.5 * 1.7
+    bn = eb.bn_regime("plain", 32, 8)
+    r = eb.conv_ref64(x, w, stride=1, pad=1, bn=bn, relu=0)
+    got = emulate(x, w, g, bn, None, 0, "bf16x3")
+    return x, w, bn, g, r, got
+
+
+def test_fault_free_baseline(fault_case):
+    x, w, bn, g, r, got = fault_case
+    assert rel(got, r.ref) <= 1e-5
+    assert eb.check_elementwise(got, r, "bf16x3") <= 0.5
+
+
+def _fails(got, r, factor=4.0):
+    worst, _ = eb.elementwise_ratio(got, r, "bf16x3")
+    return worst
+
+
+def test_fault_strip_from_hi_halves(fault_case):
+    """One 16-pixel x 16-channel strip computed from the hi halves only (a lost lo operand)."""
+    x, w, bn, g, r, _ = fault_case
+    mask = torch.zeros(1, 32, 10, 64, 64, dtype=torch.bool)
+    mask[0, 16:32, 5, 40, 16:32] = True
+    bad = emulate(x, w, g, bn, None, 0, "bf16x3", hi_only=mask)
+    assert rel(bad, r.ref) <= REL_GATE["bf16x3"]      # the relative-L2 gate passes it ...
+    assert _fails(bad, r) >= 4.0                      # ... the bound does not
+
+
+def test_fault_one_missed_product(fault_case):
+    x, w, bn, g, r, got = fault_case
+    bad = got.clone()
+    s, _ = eb.fold_bn(bn, 32)
+    bad[0, 7, 3, 20, 33] -= float(x[0, 11, 3, 20, 33].double() * w[7, 11, 1, 1, 1].double() * s[7])
+    assert rel(bad, r.ref) <= REL_GATE["bf16x3"]
+    assert _fails(bad, r) >= 4.0
+
+
+def test_fault_one_element_off(fault_case):
+    x, w, bn, g, r, got = fault_case
+    s, _ = eb.fold_bn(bn, 32)
+    S = r.D[0, 3, 6, 30, 30] - r.pre.abs()[0, 3, 6, 30, 30] - 0   # |s| S + |t| (no residual): upper estimate of |s| S
+    bad = got.clone()
+    bad[0, 3, 6, 30, 30] += float(1e-3 * S)
+    assert rel(bad, r.ref) <= REL_GATE["bf16x3"]
+    assert _fails(bad, r) >= 4.0
+
+
+def test_fault_missed_tap_at_corner(fault_case):
+    """The corner pixel of a slice loses one whole tap (all input channels of filter position (1, 1, 2))."""
+    x, w, bn, g, r, got = fault_case
+    s, _ = eb.fold_bn(bn, 32)
+    bad = got.clone()
+    tap = (x[0, :, 4, 0, 1].double()[None, :] * w[:, :, 1, 1, 2].double()).sum(1) * s
+    bad[0, :, 4, 0, 0] -= tap.float()
+    assert _fails(bad, r) >= 4.0
+
+
+def test_fault_swapped_lo_fragment():
+    """One weight fragment (16 output channels x 32 K values, the packer's [part][64 lanes][8] unit) takes its lo half from the next
+    fragment along K: only 2^-9-sized terms move, over the whole output plane of those channels.  16 -> 16 channels (K = 432)."""
+    g = geo(1, 1)
+    gen = torch.Generator().manual_seed(11)
+    x = torch.rand(1, 16, 4, 32, 32, generator=gen) * 2 - 1
+    w = (torch.rand(16, 16, 3, 3, 3, generator=gen) * 2 - 1) * (2.0 / 432) ** 0.5 * 1.7
+    r = eb.conv_ref64(x, w, stride=1, pad=1)
+    xh, xl = split(x, "bf16x3")
+    wh, wl = split(w, "bf16x3")
+    # K order (tap, channel): K values 0..31 = taps 0, 1 x 16 channels; 32..63 = taps 2, 3
+    wl2 = wl.reshape(16, 16, 27).clone()
+    wl2[:, :, 0:2] = wl.reshape(16, 16, 27)[:, :, 2:4]
+    wl2 = wl2.reshape(wl.shape)
+    acc = _conv32(xh, wh, g) + _conv32(xh, wl2, g) + _conv32(xl, wh, g)
+    bad = store(acc, "bf16x3")
+    assert eb.check_elementwise(store(_conv32(xh, wh, g) + _conv32(xh, wl, g) + _conv32(xl, wh, g), "bf16x3"), r, "bf16x3") <= 0.5
+    assert _fails(bad, r) >= 4.0
+
+
+def test_pool_bounds_emulated():
+    gen = torch.Generator().manual_seed(3)
+    x = torch.rand(2, 16, 3, 16, 32, generator=gen) * 2 - 1
+    for prec in ("bf16x3", "fp16", "bf16"):
+        xs = store(x, prec)
+        assert eb.check_elementwise(store(F.max_pool3d(xs, (1, 2, 2), (1, 2, 2)), prec), eb.pool_ref64(x, 2, "max"), prec) <= 0.5
+        for k in (2, 4, 8):
+            got = store(F.avg_pool3d(xs, (1, k, k), (1, k, k)), prec)
+            assert eb.check_elementwise(got, eb.pool_ref64(x, k, "avg"), prec) <= 0.5
+
+
+def test_score_bound_emulated():
+    """The fused classifier: scores from the stored y with rounded classifier weights, fp32 sum."""
+    x, w, bn, res, relu = make_case(CASES[2], "trained_bn")
+    g = CASES[2][4]
+    r = eb.conv_ref64(x, w, stride=g["stride"], pad=g["pad"], transposed=True, bn=bn, residual=res, relu=relu)
+    cw = torch.rand(1, 16, 1, 1, 1, generator=torch.Generator().manual_seed(5)) * 2 - 1
+    rs = eb.score_ref64(r, cw)
+    for prec in ("bf16x3", "fp16", "bf16"):
+        y = emulate(x, w, g, bn, res, relu, prec)
+        ch, cl = split(cw.reshape(1, 16, 1, 1, 1), prec)
+        yh, yl = split(y, prec)
+        sc = (yh * ch + yh * cl + yl * ch).sum(1)
+        assert eb.check_elementwise(sc, rs, prec) <= 0.5
+        bad = sc.clone()
+        bad[0, 1, 3, 5] -= float(y[0, 4, 1, 3, 5] * cw.reshape(-1)[4])   # one channel's term lost
+        assert eb.elementwise_ratio(bad, rs, prec)[0] >= 4.0 or prec != "bf16x3"
+
+
+def test_nan_and_nonzero_outside_footprint_fail():
+    x = eb.impulse_input(1, 8, 3, 16, 16)
+    w = torch.rand(8, 8, 3, 3, 3, generator=torch.Generator().manual_seed(1)) - 0.5
+    r = eb.conv_ref64(x, w, pad=1)
+    got = r.ref.float().clone()
+    assert eb.check_elementwise(got, r, "bf16x3") <= 1.0
+    far = (r.D == 0).nonzero()[0].tolist()
+    bad = got.clone()
+    bad[tuple(far)] = 1e-30
+    with pytest.raises(AssertionError, match="over the bound"):
+        eb.check_elementwise(bad, r, "bf16x3")
+    bad = got.clone()
+    bad[0, 0, 0, 0, 0] = float("nan")
+    with pytest.raises(AssertionError, match="over the bound"):
+        eb.check_elementwise(bad, r, "bf16x3")

@@ -20,6 +20,19 @@ TAP_TOL = {"bf16x3": 2e-4}
 # volumes V1 / V2 / V3 (measured <= 1.5e-5).
 DRIFT_OUT = 2e-4
 DRIFT_TAP = {"V1": 5e-5, "V2": 5e-5, "V3": 5e-5}
+# per-pixel guards: the gates above are relative L2, which one wrong pixel barely moves.  max |out - golden| over the golden's outputs,
+# ~4x above the measured value (MI355X, split-bf16; in brackets): batch2_bcast 1e-3 (2.6e-4), ddff_5x224 2.2e-3 (5.5e-4), full2_10x256
+# 3e-3 (7.6e-4), full_10x256 3.3e-3 (8.2e-4), he_10x256 7.5e-3 (1.9e-3), he_n10_64 6.5e-3 (1.6e-3), n15_wide 1e-3 (2.5e-4), one_slice
+# 3e-8 (7.5e-9: one slice, the depth is the focus distance), tiny_taps 4.4e-4 (1.1e-4)
+PIXEL_OUT = {"den_batch2_bcast": 1e-3, "den_ddff_5x224": 2.2e-3, "den_full2_10x256": 3e-3, "den_full_10x256": 3.3e-3, "den_he_10x256": 7.5e-3,
+             "den_he_n10_64": 6.5e-3, "den_n15_wide": 1e-3, "den_one_slice": 3e-8, "den_tiny_taps": 4.4e-4}
+# and of the taps of den_tiny_taps, max |tap - golden| / max |golden|, ~4x above the measured value: V1 1.1e-5, V2 1.6e-5, V3 1.4e-5,
+# FS_volume 1.7e-5, conf 1.9e-5, cost1 1.2e-5, cost2 1.4e-5, cost3 1.6e-5
+PIXEL_TAP = {"V1": 4.5e-5, "V2": 6.5e-5, "V3": 6e-5, "FS_volume": 7e-5, "conf": 7.5e-5, "cost1": 5e-5, "cost2": 5.5e-5, "cost3": 6.5e-5}
+
+
+def max_abs(a, b):
+    return float((a.cpu().double() - torch.as_tensor(b).double()).abs().max())
 
 
 def case(path):
@@ -62,6 +75,8 @@ def test_forward_matches_reference_goldens(lib_built, path):
             assert err <= OUT_TOL["bf16x3"], (name, err)
             if name == "pred3":
                 assert err <= DRIFT_OUT, ("drift guard", name, err)
+            px = max_abs(o, g[name])
+            assert px <= PIXEL_OUT[os.path.basename(path)[:-4]], ("per-pixel guard", name, px)
 
 
 def test_intermediate_volumes_match_goldens(lib_built):
@@ -76,6 +91,8 @@ def test_intermediate_volumes_match_goldens(lib_built):
         assert err <= TAP_TOL["bf16x3"], (nm, err)
         if nm in DRIFT_TAP:
             assert err <= DRIFT_TAP[nm], ("drift guard", nm, err)
+        px = max_abs(taps[nm], g["tap_" + nm]) / float(np.abs(g["tap_" + nm]).max())
+        assert px <= PIXEL_TAP[nm], ("per-pixel guard", nm, px)
 
 
 def test_debug_flag_without_fill_is_an_error_not_an_abort(lib_built, monkeypatch):
@@ -475,3 +492,51 @@ def test_alternative_kernel_paths_keep_parity(lib_built, env, which, monkeypatch
             assert err <= OUT_TOL["bf16x3"], (env, name, err)
             if name == "pred3":
                 assert err <= DRIFT_OUT, ("drift guard", env, name, err)
+
+
+def _poisoned_then_zeroed(engine, run, ws_shape):
+    """Run ``run()`` (-> list of tensors) on the engine's cached workspace filled with 0xFF bytes (NaN in fp32, bf16 and fp16), then
+    filled with zeros: every output must be finite and bit-identical between the two.  Fresh device memory usually comes back zeroed
+    and zero is the padding value, so a missing halo or footprint fill, or an element no kernel stores, would otherwise pass."""
+    run()                                       # sizes and caches the workspace
+    torch.cuda.synchronize()
+    ws = engine._workspace(*ws_shape)
+    ptr = ws.data_ptr()
+    ws.fill_(0xFF)
+    poisoned = [t.clone() for t in run()]
+    torch.cuda.synchronize()
+    assert engine._workspace(*ws_shape).data_ptr() == ptr   # the forward ran on the poisoned block
+    ws.zero_()
+    zeroed = [t.clone() for t in run()]
+    torch.cuda.synchronize()
+    assert len(poisoned) == len(zeroed)
+    for i, (a, b) in enumerate(zip(poisoned, zeroed)):
+        assert torch.isfinite(a).all(), i
+        assert torch.equal(a, b), (i, float((a - b).abs().max()))
+
+
+TAP_NAMES = ("V1", "V2", "V3", "FS_volume", "conf", "cost1", "cost2", "cost3")
+
+
+@pytest.mark.parametrize("shape", ["tiny_taps", "he_n10_64", (1, 7, 96, 160, 11)], ids=str)
+def test_forward_on_poisoned_workspace(lib_built, shape):
+    """The forward's outputs and taps do not depend on what the workspace held before: streaming, team and edge-tile paths."""
+    if isinstance(shape, str):
+        g, meta, FS, fd, sd = case([p for p in GOLDEN if shape in p][0])
+        model = model_for(sd, (meta["wseed"], meta["profile"]))
+    else:
+        B, N, H, W, seed = shape
+        entries = list(graph.param_entries(graph.dff_net_convs()))
+        sd = {k: torch.from_numpy(v) for k, v in synth.state_dict_numpy(entries, 7, "smooth").items()}
+        FS = torch.from_numpy(synth.focal_stack(B, N, H, W, seed=seed))
+        fd = torch.from_numpy(synth.focus_dists(B, N, H, W))
+        model = model_for(sd, (7, "smooth"))
+    FS, fd = FS.cuda(), fd.cuda()
+    B, _, N, H, W = FS.shape
+    engine = model._engine_on(FS.device)
+
+    def run():
+        with torch.no_grad():
+            outs, taps = model.forward_with_taps(FS, fd, TAP_NAMES)
+        return list(outs) + [taps[nm] for nm in TAP_NAMES]
+    _poisoned_then_zeroed(engine, run, (B, N, H, W))

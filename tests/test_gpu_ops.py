@@ -1,9 +1,16 @@
 """GPU: each kernel family of libdffw.so, called through the C ABI, against the same PyTorch
 operator the reference invokes (computed on the CPU in fp32).  Tolerances are relative L2:
-split-bf16 5e-5 (expected ~1e-5), fp16 3e-3, bf16 2e-2."""
+split-bf16 5e-5 (expected ~1e-5), fp16 3e-3, bf16 2e-2.  Every conv and pool result is also held elementwise to the forward-error
+bound of oracle/error_bounds.py against a float64 reference (``|got - ref| <= alpha_prec * D``), and two kernels' results of one op to
+twice that bound; the op path runs on a workspace poisoned with NaN, so every result must also be finite."""
+import json
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+from oracle import error_bounds as eb
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +42,53 @@ def bn_params(c, seed):
 
 def ref_bn(y, bn):
     return F.batch_norm(y, bn[2], bn[3], bn[0], bn[1], False, 0.0, 1e-5)
+
+
+_R64 = {}
+WORST = {}   # (kernel family, precision) -> max err / bound seen in this module
+
+
+def ref64(key, x, w, **kw):
+    """eb.conv_ref64 of one case, cached so that got, alt and the three precisions of the case share one float64 computation."""
+    if key not in _R64:
+        _R64.clear()
+        _R64[key] = eb.conv_ref64(x, w, **kw)
+    return _R64[key]
+
+
+def family(kernel):
+    return kernel.split("<")[0].replace("dffw::", "")
+
+
+def bounded(got, r, prec, kernel, what="got"):
+    """Finite everywhere (the op's workspace is poisoned with NaN) and within the per-element bound; logs the worst ratio."""
+    assert torch.isfinite(got).all(), (what, kernel)
+    worst = eb.check_elementwise(got, r, prec, "%s %s" % (what, kernel))
+    k = (family(kernel), prec)
+    WORST[k] = max(WORST.get(k, 0.0), worst)
+    return worst
+
+
+def paired(got, alt, r, prec, what="got vs alt"):
+    """Two kernels' results of one op agree elementwise to twice the bound."""
+    return eb.check_pair(got, alt, r, prec, what)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def worst_ratio_report():
+    """With ERROR_BOUND_REPORT=<file>, the worst err / bound per kernel family and precision is written there as JSON."""
+    yield
+    path = os.environ.get("ERROR_BOUND_REPORT")
+    if path:
+        old = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                old = json.load(f)
+        for (fam, prec), v in WORST.items():
+            key = "%s/%s" % (fam, prec)
+            old[key] = max(old.get(key, 0.0), v)
+        with open(path, "w") as f:
+            json.dump(old, f, indent=1, sort_keys=True)
 
 
 # (name, Cin, Cout, kernel, stride, pad, dilation, N, H, W)  — every conv family of DFF_net (SURVEY.md 8a)
@@ -76,6 +130,8 @@ def test_conv_families(eng, case, prec):
         ref = ref.squeeze(1)
     assert got.shape == ref.shape
     assert rel(got, ref) <= TOL[prec], (name, prec, rel(got, ref))
+    r = ref64(("families", name), x, w, stride=s, pad=p, dilation=d, bn=bn, relu=1 if bn else 0)
+    bounded(got, r.squeeze1() if cout == 1 else r, prec, eng.last_conv_kernel())
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
@@ -100,11 +156,15 @@ def test_conv_roll_strided_16_channels(eng, cin, cout, B, N, H, W, relu, wgs, pr
     got = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=relu, precision=prec)
     assert eng.last_conv_kernel().startswith("dffw::conv_roll_s2<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("roll_s2", cin, cout, B, N, H, W, relu), x, w, stride=(1, 2, 2), pad=1, bn=bn, relu=relu)
+    bounded(got, r, prec, eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_ROLL_S2", "1")
     alt = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=relu, precision=prec)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
     assert rel(got, alt) <= TOL[prec] * 0.2
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 SMALL_CASES = [
@@ -152,11 +212,16 @@ def test_conv_small_grids(eng, case, prec, monkeypatch):
         ref = ref.squeeze(1)
     assert got.shape == ref.shape
     assert rel(got, ref) <= TOL[prec], (name, rel(got, ref))
+    r = ref64(("small", name), x, w, stride=st, pad=pd, transposed=transposed, bn=bn, residual=res, relu=1 if bn else 0)
+    r = r.squeeze1() if cout == 1 else r
+    bounded(got, r, prec, eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_SMALL", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_igemm<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
     assert rel(got, alt) <= TOL[prec] * 0.2
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 TEAM_CASES = [
@@ -194,6 +259,8 @@ def test_conv_tile_teams(eng, case, prec, monkeypatch):
     kn = eng.last_conv_kernel()
     assert kn.startswith("dffw::conv_tile<") and kn.endswith(", %d>" % kt), kn   # (last template argument: teams per workgroup)
     assert rel(got, ref) <= TOL[prec], (name, rel(got, ref))
+    r = ref64(("teams", name), x, w, stride=(1, stride, stride), pad=1, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, "dffw::conv_tile_teams<")
     again = eng.op_conv3d(x.cuda(), w, **kw)
     assert torch.equal(got, again)
     monkeypatch.setenv("DFFW_NO_TEAMS", "1")
@@ -202,6 +269,8 @@ def test_conv_tile_teams(eng, case, prec, monkeypatch):
     assert kn.startswith("dffw::conv_tile<") and kn.endswith(", true, false, 1>"), kn   # the split-K instantiation
     assert rel(alt, ref) <= TOL[prec]
     assert rel(got, alt) <= TOL[prec] * 0.1, rel(got, alt)
+    bounded(alt, r, prec, "dffw::conv_tile_splitk<", "alt")
+    paired(got, alt, r, prec)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
@@ -224,12 +293,16 @@ def test_conv_tile_teams_transposed(eng, cin, cout, B, N, H, W, residual, kt, pr
     kn = eng.last_conv_kernel()
     assert kn.startswith("dffw::conv_tile<0, 2," if prec == "bf16x3" else "dffw::conv_tile<") and kn.endswith(", %d>" % kt), kn
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("teams_t", cin, cout, B, N, H, W, residual), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, "dffw::conv_tile_teams_t<")
     assert torch.equal(got, eng.op_conv3d(x.cuda(), w, **kw))
     monkeypatch.setenv("DFFW_NO_TEAMS", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().endswith(", 1>"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
     assert rel(got, alt) <= TOL[prec] * 0.1, rel(got, alt)
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
@@ -258,15 +331,21 @@ def test_conv_roll_rolling_window(eng, cout, N, H, W, zsplit, residual, wgs, pre
     pipelined = cout == 8 and not residual and prec == "bf16x3"
     assert eng.last_conv_kernel().startswith("dffw::conv_rollx_pair<" if pipelined else "dffw::conv_roll<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("roll", cout, N, H, W, residual), x, w, pad=1, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, eng.last_conv_kernel())
     if pipelined:   # ... and the serial step must give the same values (three accumulators instead of two: fp32 re-association only)
         monkeypatch.setenv("DFFW_NO_ROLLX", "1")
         old = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, residual=None, relu=1, precision=prec)
         assert eng.last_conv_kernel().startswith("dffw::conv_roll<"), eng.last_conv_kernel()
         assert rel(got, old) <= 2e-6, rel(got, old)
+        bounded(old, r, prec, eng.last_conv_kernel(), "serial")
+        paired(got, old, r, prec)
     monkeypatch.setenv("DFFW_NO_ROLL", "1")
     alt = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, residual=res.cuda() if residual else None, relu=1, precision=prec)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 @pytest.mark.parametrize("N,H,W,zsplit,wgs,relu", [(10, 128, 128, 1, 0, 1), (1, 64, 256, 1, 8, 1), (7, 64, 256, 3, 24, 0), (2, 128, 128, 2, 16, 1), (3, 128, 128, 3, 8, 1),
@@ -289,10 +368,14 @@ def test_conv_rollx_k2(eng, N, H, W, zsplit, wgs, relu, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, relu=relu, precision="bf16x3")
     assert eng.last_conv_kernel().startswith("dffw::conv_rollx_k2<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL["bf16x3"], rel(got, ref)
+    r = ref64(("rollx_k2", N, H, W, relu), x, w, pad=1, bn=bn, relu=relu)
+    bounded(got, r, "bf16x3", eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_ROLLX", "1")
     alt = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, relu=relu, precision="bf16x3")
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(got, alt) <= 2e-5, rel(got, alt)
+    bounded(alt, r, "bf16x3", eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, "bf16x3")
 
 
 @pytest.mark.parametrize("B,N,H,W,wgs,relu,residual", [(3, 10, 64, 64, 0, 1, False), (2, 1, 32, 64, 8, 1, True), (3, 7, 64, 32, 24, 0, True), (2, 2, 40, 48, 16, 1, False),
@@ -319,10 +402,14 @@ def test_conv_slice32(eng, B, N, H, W, wgs, relu, residual, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_slice32<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL["bf16x3"], rel(got, ref)
+    r = ref64(("slice32", B, N, H, W, relu, residual), x, w, pad=(0, 1, 1), bn=bn, residual=res, relu=relu)
+    bounded(got, r, "bf16x3", eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_SLICE32", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(got, alt) <= 2e-5, rel(got, alt)
+    bounded(alt, r, "bf16x3", eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, "bf16x3")
 
 
 @pytest.mark.parametrize("B,N,H,W,wgs,relu", [(3, 10, 64, 64, 0, 1), (2, 1, 32, 64, 8, 1), (3, 7, 64, 32, 24, 0), (2, 2, 40, 48, 16, 1), (5, 3, 8, 16, 0, 0), (1, 5, 120, 160, 0, 1)])
@@ -345,12 +432,16 @@ def test_conv_slice64(eng, B, N, H, W, wgs, relu, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_slice64<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL["bf16x3"], rel(got, ref)
+    r = ref64(("slice64", B, N, H, W, relu), x, w, pad=(0, 1, 1), bn=bn, relu=relu)
+    bounded(got, r, "bf16x3", eng.last_conv_kernel())
     again = eng.op_conv3d(x.cuda(), w, **kw)
     assert torch.equal(got, again)
     monkeypatch.setenv("DFFW_NO_SLICE32", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(got, alt) <= 2e-5, rel(got, alt)
+    bounded(alt, r, "bf16x3", eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, "bf16x3")
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 32), (32, 32), (64, 64), (32, 64)])
@@ -381,6 +472,8 @@ def test_conv_rollk(eng, cin, cout, N, H, W, zsplit, wgs, relu, residual, monkey
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_rollk<%d," % (cin // 8)), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL["bf16x3"], rel(got, ref)
+    r = ref64(("rollk", cin, cout, N, H, W, relu, residual), x, w, pad=1, bn=bn, residual=res, relu=relu)
+    bounded(got, r, "bf16x3", eng.last_conv_kernel())
     again = eng.op_conv3d(x.cuda(), w, **kw)
     assert torch.equal(got, again)                      # the partial sums are added in a fixed order
     if cout == 64:                                      # the two 32-channel output halves as two launches instead of grid.y = 2 of one: same arithmetic
@@ -393,6 +486,8 @@ def test_conv_rollk(eng, cin, cout, N, H, W, zsplit, wgs, relu, residual, monkey
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert not eng.last_conv_kernel().startswith("dffw::conv_rollk<"), eng.last_conv_kernel()
     assert rel(got, alt) <= 2e-5, rel(got, alt)
+    bounded(alt, r, "bf16x3", eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, "bf16x3")
 
 
 ROLLT_SHAPES = [(10, 32, 32, 0, 1, False), (1, 16, 24, 8, 1, True), (7, 24, 16, 24, 0, True), (2, 30, 40, 16, 1, False), (3, 8, 8, 0, 0, False),
@@ -427,12 +522,16 @@ def test_conv_rollt(eng, cin, cout, N, H, W, wgs, relu, residual, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel() == "dffw::conv_rollt<%d, %d, %s>" % (cin, 1 if residual else 0, "true" if cout == 16 else "false"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL["bf16x3"], rel(got, ref)
+    r = ref64(("rollt", cin, cout, N, H, W, relu, residual), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=relu)
+    bounded(got, r, "bf16x3", eng.last_conv_kernel())
     again = eng.op_conv3d(x.cuda(), w, **kw)
     assert torch.equal(got, again)                      # the K-split pair adds its two partials in a fixed order
     monkeypatch.setenv("DFFW_NO_ROLLT", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith(("dffw::conv_tile<", "dffw::conv_roll_t32<")), eng.last_conv_kernel()
     assert rel(got, alt) <= 2e-5, rel(got, alt)
+    bounded(alt, r, "bf16x3", eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, "bf16x3")
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 32), (32, 32), (32, 16), (16, 16)])
@@ -465,12 +564,30 @@ def test_conv_rollt_second_output_and_classifier(eng, cin, cout, N, H, W, wgs, r
         assert rel(yp, ref_pre) <= TOL["bf16x3"], rel(yp, ref_pre)
     if cls:
         assert rel(sc, ref_cls) <= TOL["bf16x3"], rel(sc, ref_cls)
+    r = ref64(("rollt2", cin, cout, N, H, W, relu), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=relu)
+    rp = eb.Ref64(r.pre, r.pre, r.D - res.double().abs(), r.sub)   # y_pre: BN(conv), before the residual
+    rs = eb.score_ref64(r, cw)
+    kn = eng.last_conv_kernel()
+    bounded(y, r, "bf16x3", kn)
+    if pre:
+        bounded(yp, rp, "bf16x3", kn, "y_pre")
+    if cls:
+        bounded(sc, rs, "bf16x3", kn, "score")
     y2, yp2, sc2 = eng.op_conv3d(x.cuda(), w, **kw)
     assert torch.equal(y, y2) and (not pre or torch.equal(yp, yp2)) and (not cls or torch.equal(sc, sc2))
     monkeypatch.setenv("DFFW_NO_ROLLT", "1")
     ya, ypa, sca = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith(("dffw::conv_tile<", "dffw::conv_roll_t32<")), eng.last_conv_kernel()
     assert rel(y, ya) <= 2e-5 and (not pre or rel(yp, ypa) <= 2e-5) and (not cls or rel(sc, sca) <= 2e-5)
+    kn = eng.last_conv_kernel()
+    bounded(ya, r, "bf16x3", kn, "alt")
+    paired(y, ya, r, "bf16x3")
+    if pre:
+        bounded(ypa, rp, "bf16x3", kn, "alt y_pre")
+        paired(yp, ypa, rp, "bf16x3", "y_pre vs alt")
+    if cls:
+        bounded(sca, rs, "bf16x3", kn, "alt score")
+        paired(sc, sca, rs, "bf16x3", "score vs alt")
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
@@ -495,10 +612,14 @@ def test_conv_roll_transposed(eng, N, H, W, zsplit, residual, wgs, prec, monkeyp
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_roll_t<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("roll_t", N, H, W, residual), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_ROLL", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 def test_no_lean_roll_switch_reaches_every_rolling_kernel(eng, monkeypatch):
@@ -546,10 +667,14 @@ def test_conv_roll_transposed_32(eng, N, H, W, residual, wgs, cin, prec, monkeyp
     got = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_roll_t32<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("roll_t32", cin, N, H, W, residual), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_ROLL", "1")
     alt = eng.op_conv3d(x.cuda(), w, **kw)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
@@ -567,10 +692,14 @@ def test_conv_roll_strided(eng, N, H, W, wgs, prec, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=1, precision=prec)
     assert eng.last_conv_kernel().startswith("dffw::conv_roll_efd<"), eng.last_conv_kernel()
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("roll_efd", N, H, W), x, w, stride=(1, 2, 2), pad=1, bn=bn, relu=1)
+    bounded(got, r, prec, eng.last_conv_kernel())
     monkeypatch.setenv("DFFW_NO_ROLL", "1")
     alt = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=1, precision=prec)
     assert eng.last_conv_kernel().startswith("dffw::conv_tile<"), eng.last_conv_kernel()
     assert rel(alt, ref) <= TOL[prec]
+    bounded(alt, r, prec, eng.last_conv_kernel(), "alt")
+    paired(got, alt, r, prec)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16"])
@@ -585,6 +714,8 @@ def test_transposed_conv_phases(eng, cin, cout, N, H, W, prec):
     ref = F.relu(ref_bn(F.conv_transpose3d(x, w, None, (1, 2, 2), 1, (0, 1, 1)), bn) + res)
     got = eng.op_conv3d(x.cuda(), w, transposed=True, stride=(1, 2, 2), pad=1, bn=bn, residual=res.cuda(), relu=1, precision=prec)
     assert rel(got, ref) <= TOL[prec], rel(got, ref)
+    r = ref64(("phases", cin, cout, N, H, W), x, w, stride=(1, 2, 2), pad=1, transposed=True, bn=bn, residual=res, relu=1)
+    bounded(got, r, prec, eng.last_conv_kernel())
 
 
 def test_conv_epilogue_variants(eng):
@@ -596,6 +727,9 @@ def test_conv_epilogue_variants(eng):
     assert rel(eng.op_conv3d(x.cuda(), w, residual=res.cuda(), relu=2), F.relu(y) + res) <= 5e-5
     assert rel(eng.op_conv3d(x.cuda(), w, residual=res.cuda(), relu=0), y + res) <= 5e-5
     assert rel(eng.op_conv3d(x.cuda(), w, residual=res.cuda(), relu=1), F.relu(y + res)) <= 5e-5
+    for relu in (2, 0, 1):
+        got = eng.op_conv3d(x.cuda(), w, residual=res.cuda(), relu=relu)
+        bounded(got, eb.conv_ref64(x, w, residual=res, relu=relu), "bf16x3", eng.last_conv_kernel(), "relu=%d" % relu)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16"])
@@ -604,6 +738,9 @@ def test_pools(eng, prec):
     assert rel(eng.op_pool(x.cuda(), 2, "max", prec), F.max_pool3d(x, (1, 2, 2), (1, 2, 2))) <= TOL[prec]
     for k in (2, 4, 8):
         assert rel(eng.op_pool(x.cuda(), k, "avg", prec), F.avg_pool3d(x, (1, k, k), (1, k, k))) <= TOL[prec]
+    bounded(eng.op_pool(x.cuda(), 2, "max", prec), eb.pool_ref64(x, 2, "max"), prec, "pool_max<", "max")
+    for k in (2, 4, 8):
+        bounded(eng.op_pool(x.cuda(), k, "avg", prec), eb.pool_ref64(x, k, "avg"), prec, "pool_avg<", "avg k=%d" % k)
 
 
 def test_softplus_pointwise_sweep(eng):
@@ -650,3 +787,73 @@ def test_regression_head(eng, N, h, w, scale, layout):
     got = eng.op_regress(score.cuda(), fd_in.cuda(), H, W)
     assert rel(got, ref) <= 2e-6, rel(got, ref)
     assert float((got.cpu() - ref).abs().max()) <= 5e-6
+
+
+ALL3 = ("bf16x3", "fp16", "bf16")
+# One row per conv kernel family the op path reaches: (name, Cin, Cout, kernel, stride, pad, dilation, transposed, (B, N, H, W), residual,
+# relu, DFFW_* switches that force the family, kernel-name prefixes it must report, precisions).  Shapes are edge-tile shapes from the
+# family's own test above; switches as there.
+WIDE_ROWS = [
+    ("tile_generic", 16, 16, (3, 3, 3), 1, 1, 1, False, (1, 2, 40, 48), True, 1, {"DFFW_NO_ROLL": "1", "DFFW_NO_LEAN_TILE": "1"}, ("dffw::conv_tile<",), ALL3),
+    ("tile_lean", 16, 16, (3, 3, 3), 1, 1, 1, False, (1, 2, 40, 48), False, 1, {"DFFW_NO_ROLL": "1"}, ("dffw::conv_tile<",), ALL3),
+    ("tile_teams", 64, 64, (3, 3, 3), 1, 1, 1, False, (2, 3, 8, 8), True, 1, {"DFFW_ROLL_MIN_UNITS": "100000", "DFFW_TEAM_MAX_WGS": "100000"},
+     ("dffw::conv_tile<",), ALL3),
+    ("igemm", 32, 64, (3, 3, 3), 1, 1, 1, False, (2, 3, 7, 5), False, 1, {"DFFW_NO_SMALL": "1"}, ("dffw::conv_igemm<",), ALL3),
+    ("small", 32, 64, (3, 3, 3), 1, 1, 1, False, (2, 3, 7, 5), True, 1, {}, ("dffw::conv_small<",), ALL3),
+    ("small_t", 128, 64, (3, 3, 3), (1, 2, 2), 1, 1, True, (1, 3, 7, 7), True, 1, {}, ("dffw::conv_small<",), ALL3),
+    ("roll8", 16, 8, (3, 3, 3), 1, 1, 1, False, (2, 2, 128, 128), True, 1, {"DFFW_ROLL_ZSPLIT": "2", "DFFW_ROLL_WGS": "16"},
+     ("dffw::conv_roll<", "dffw::conv_rollx_pair<"), ALL3),   # (the impulse regime has no residual: in split-bf16 the pipelined step)
+    ("roll_s2", 16, 32, (3, 3, 3), (1, 2, 2), 1, 1, False, (4, 1, 128, 64), False, 0, {"DFFW_ROLL_WGS": "16"}, ("dffw::conv_roll_s2<",), ALL3),
+    ("rollx_pair", 16, 8, (3, 3, 3), 1, 1, 1, False, (2, 2, 128, 128), False, 1, {"DFFW_ROLL_ZSPLIT": "2", "DFFW_ROLL_WGS": "16"},
+     ("dffw::conv_rollx_pair<",), ("bf16x3",)),
+    ("rollx_k2", 32, 16, (3, 3, 3), 1, 1, 1, False, (2, 2, 128, 128), False, 1, {"DFFW_ROLL_ZSPLIT": "2", "DFFW_ROLL_WGS": "16"},
+     ("dffw::conv_rollx_k2<",), ("bf16x3",)),
+    ("slice32", 32, 32, (1, 3, 3), 1, (0, 1, 1), 1, False, (5, 3, 8, 16), True, 1, {"DFFW_ROLL_MIN_UNITS": "1"}, ("dffw::conv_slice32<",), ("bf16x3",)),
+    ("slice64", 64, 64, (1, 3, 3), 1, (0, 1, 1), 1, False, (2, 2, 40, 48), False, 1, {"DFFW_ROLL_MIN_UNITS": "1", "DFFW_ROLL_WGS": "16"},
+     ("dffw::conv_slice64<",), ("bf16x3",)),
+    ("rollk", 64, 32, (3, 3, 3), 1, 1, 1, False, (3, 4, 28, 36), True, 1, {"DFFW_ROLL_MIN_UNITS": "1", "DFFW_ROLL_ZSPLIT": "2", "DFFW_ROLL_WGS": "8"},
+     ("dffw::conv_rollk<",), ("bf16x3",)),
+    ("rollt", 64, 32, (3, 3, 3), (1, 2, 2), 1, 1, True, (3, 4, 14, 18), True, 0, {"DFFW_ROLL_MIN_UNITS": "1", "DFFW_ROLL_WGS": "8"},
+     ("dffw::conv_rollt<",), ("bf16x3",)),
+    ("rollt_wide", 32, 16, (3, 3, 3), (1, 2, 2), 1, 1, True, (3, 2, 30, 40), False, 1, {"DFFW_ROLL_MIN_UNITS": "1", "DFFW_ROLL_WGS": "16"},
+     ("dffw::conv_rollt<",), ("bf16x3",)),
+    ("roll_t", 16, 8, (3, 3, 3), (1, 2, 2), 1, 1, True, (2, 1, 64, 256), True, 1, {"DFFW_ROLL_WGS": "8"}, ("dffw::conv_roll_t<",), ALL3),
+    ("roll_t32", 32, 16, (3, 3, 3), (1, 2, 2), 1, 1, True, (2, 1, 128, 128), False, 1, {"DFFW_ROLL_WGS": "8", "DFFW_NO_ROLLT": "1"},
+     ("dffw::conv_roll_t32<",), ALL3),
+    ("roll_efd", 8, 16, (3, 3, 3), (1, 2, 2), 1, 1, False, (2, 1, 128, 256), False, 1, {"DFFW_ROLL_WGS": "8"}, ("dffw::conv_roll_efd<",), ALL3),
+    ("stem", 3, 8, (1, 9, 9), 1, (0, 8, 8), (1, 2, 2), False, (2, 3, 32, 40), False, 1, {}, ("dffw::stem_pipe<", "dffw::conv_tile<"), ALL3),
+]
+_WIDE = [(row, rg, prec) for row in WIDE_ROWS for rg in eb.REGIMES for prec in row[13]]
+
+
+@pytest.mark.parametrize("row,regime,prec", _WIDE, ids=["%s-%s-%s" % (r[0], g, p) for r, g, p in _WIDE])
+def test_conv_kernels_wide_regimes(eng, row, regime, prec, monkeypatch):
+    """Every conv family of the op path on the inputs and BatchNorm statistics where kernels go wrong, elementwise against the float64
+    bound: unit impulses at corners, tile boundaries, first / last slice and channel (the output is the filter footprint: a wrong tap,
+    phase or channel mapping shows, and wherever D == 0 the result must be exactly 0 -- NaN from uninitialised LDS or a padding value
+    times a zero weight fails too); per-channel constant planes (only the border differs); post-ReLU inputs (half exact zeros); a large
+    common offset cancelled by the BN mean; trained-like BN (gamma 0, negative, up to +-2; var 1e-4 ... 1e2; mean, beta within +-3).
+    The synthetic weights and bn_params above never leave gamma, var in [0.5, 1.5]."""
+    name, cin, cout, k, st, pd, dl, transposed, (B, N, H, W), residual, relu, env, prefixes, _ = row
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    x = eb.regime_input(regime, (B, cin, N, H, W), seed=101)
+    wshape = (cin, cout, *k) if transposed else (cout, cin, *k)
+    K = cin * k[0] * k[1] * k[2] // (4 if transposed else 1)
+    w = rnd(*wshape, seed=102, scale=(2.0 / K) ** 0.5 * 1.7)
+    conv_mean = 3.0 * float(w.sum()) / cout / (4 if transposed else 1) if regime == "offset" else 0.0
+    bn = eb.bn_regime(regime, cout, 103, conv_mean=conv_mean)
+    geo = dict(stride=st, pad=pd, dilation=dl, transposed=transposed)
+    r = ref64(("wide", name, regime), x, w, **geo, bn=bn, relu=relu)
+    res = None
+    if residual and regime != "impulse":
+        res = rnd(*r.ref.shape, seed=104)
+        r = ref64(("wide_res", name, regime), x, w, **geo, bn=bn, residual=res, relu=relu)
+    assert float(r.ref.abs().max()) < 1e4
+    got = eng.op_conv3d(x.cuda(), w, **geo, bn=bn, residual=res.cuda() if res is not None else None, relu=relu, precision=prec)
+    kn = eng.last_conv_kernel()
+    assert kn.startswith(prefixes), kn
+    bounded(got, r, prec, kn, "%s %s" % (name, regime))
+    if regime == "impulse":
+        zero = r.D == 0
+        assert bool(zero.any()) and torch.equal(got.cpu()[zero], torch.zeros(int(zero.sum()))), (name, kn)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -28,6 +29,7 @@ namespace dffw {
 // ---- errors ------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 static thread_local std::string g_last_kernel;   // dffw_last_conv_kernel()
+static thread_local std::string g_last_op_kernels;   // dffw_last_op_kernels()
 static int fail(int code, const char *fmt, ...) {
     char buf[1024];
     va_list ap;
@@ -1741,13 +1743,16 @@ static int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst
         r.drop(in);
         r.drop_raw(tmp);
     }
+    r.tap("stem", stem);
     Act v1p, v2p;   // max-pooled copies written by the attention kernels on the way (EFD's second branch)
     Act v1 = srd(r, P + ".FM_measure.Focus_extraction.2", stem, true, &v1p);
     r.tap("V1", v1);
     Act e1 = efd(r, P + ".FM_conv1.0", v1, &v1p);
+    r.tap("E1", e1);
     Act v2 = srd(r, P + ".FM_conv1.1", e1, true, &v2p);
     r.tap("V2", v2);
     Act e2 = efd(r, P + ".FM_conv2.0", v2, &v2p);
+    r.tap("E2", e2);
     Act v3 = srd(r, P + ".FM_conv2.1", e2, true);
     r.tap("V3", v3);
 
@@ -2521,6 +2526,102 @@ int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int
     (void)hipFree(a);
     (void)hipFree(b);
     return rc;
+}
+
+// ---- block entry points (test-only): one SRD / EFD block of the front end through the graph's own srd() / efd() ----------------
+// The block's convs are packed under the keys the graph looks up (the forward's own layer names), so the shape-keyed branches of
+// pack_conv give the fused kernels the fragment sets they get in the forward, and the dispatch is srd() / efd() itself.
+const char *dffw_last_op_kernels(void) { return g_last_op_kernels.c_str(); }
+
+// Runs `body` twice on a private engine: a dry run sizes the workspace (as dffw_workspace_bytes does), the real run gets it filled with
+// 0xFF (NaN in every format, as in dffw_op_conv3d_ex).  Every launch of the real run is profiled; their kernel names, in launch order,
+// become dffw_last_op_kernels().
+static int run_block_op(dffw_engine &eng, hipStream_t s, const std::function<void(Run &)> &body) {
+    int64_t need;
+    {
+        Run d(&eng, s, true, nullptr, INT64_MAX / 2);
+        body(d);
+        if (!d.ok()) return d.err;
+        need = d.arena.peak();
+    }
+    const int64_t bytes = need + 65536;   // (the slack a caching allocator's block would give the forward's workspace)
+    char *ws = nullptr;
+    HIPCHK(hipMalloc((void **)&ws, bytes));
+    int rc = hipMemsetAsync(ws, 0xFF, bytes, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "workspace memset");
+    if (rc == DFFW_OK) {
+        eng.profiling = true;
+        Run r(&eng, s, false, ws, bytes);
+        body(r);
+        rc = r.err;
+    }
+    const hipError_t se = hipStreamSynchronize(s);
+    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
+    for (const ProfRec &pr : eng.recs) g_last_op_kernels += (g_last_op_kernels.empty() ? "" : ";") + pr.kernel;
+    (void)hipFree(ws);
+    return rc;
+}
+
+int dffw_op_srd(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w0, const float *bn0,
+                const float *w2, const float *bn2, const float *w3, const float *w1, float *y, float *pooled, void *hip_stream) {
+    g_last_op_kernels.clear();
+    if (!x || !w0 || !bn0 || !w2 || !bn2 || !w3 || !w1 || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (C != 8 && C != 16 && C != 32) return fail(DFFW_EINVAL, "the SRD blocks have 8, 16 or 32 channels, got %d", C);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
+    if (pooled && (H % 2 || W % 2)) return fail(DFFW_EINVAL, "the pooled copy needs even H and W, got %dx%d", H, W);
+    HIPCHK(hipSetDevice(device));
+    const std::string p = C == 8 ? "DFF_net.FM_measure.Focus_extraction.2" : C == 16 ? "DFF_net.FM_conv1.1" : "DFF_net.FM_conv2.1";
+    Table t;
+    t.srd(p, C);
+    dffw_engine eng;
+    eng.device = device;
+    eng.prec = precision;
+    const float *const wts[4] = {w0, w2, w3, w1}, *const bns[4] = {bn0, bn2, nullptr, nullptr};
+    for (int i = 0; i < 4; ++i) {
+        const int rc = pack_conv(t.layers[i], precision, wts[i], bns[i], nullptr, eng.convs[t.layers[i].conv]);
+        if (rc) return rc;
+    }
+    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
+        Act in = r.act(B, N, H, W, C);
+        if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, C, N, H, W, r.s), "from_ncdhw");
+        Act pl;
+        Act out = srd(r, p, in, true, pooled ? &pl : nullptr);
+        if (pooled && !pl.p) pl = r.pool(out, 0, 2);   // (this path writes no pooled copy: the engine's pool kernel, as efd() then runs it)
+        if (r.ok() && !r.dry) {
+            r.check(launch_to_ncdhw(precision, out.p, y, B, C, N, H, W, r.s), "to_ncdhw");
+            if (pooled) r.check(launch_to_ncdhw(precision, pl.p, pooled, B, C, N, H / 2, W / 2, r.s), "to_ncdhw");
+        }
+    });
+}
+
+int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *ws, const float *bns,
+                const float *wp, const float *bnp, int pooled_at_hand, float *y, void *hip_stream) {
+    g_last_op_kernels.clear();
+    if (!x || !ws || !bns || !wp || !bnp || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (Cin != 8 && Cin != 16) return fail(DFFW_EINVAL, "the EFD blocks have 8 or 16 input channels, got %d", Cin);
+    if (B < 1 || N < 1 || H < 2 || W < 2 || H % 2 || W % 2) return fail(DFFW_EINVAL, "bad shape (H and W must be even)");
+    HIPCHK(hipSetDevice(device));
+    const std::string p = Cin == 8 ? "DFF_net.FM_conv1.0" : "DFF_net.FM_conv2.0";
+    const int Cout = 2 * Cin;
+    Table t;
+    t.efd(p, Cin, Cout);
+    dffw_engine eng;
+    eng.device = device;
+    eng.prec = precision;
+    const float *const wts[2] = {ws, wp}, *const bnv[2] = {bns, bnp};
+    for (int i = 0; i < 2; ++i) {
+        const int rc = pack_conv(t.layers[i], precision, wts[i], bnv[i], nullptr, eng.convs[t.layers[i].conv]);
+        if (rc) return rc;
+    }
+    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
+        Act in = r.act(B, N, H, W, Cin);
+        if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, r.s), "from_ncdhw");
+        Act m;   // the pooled copy "at hand", as srd() leaves it for the forward's efd()
+        if (pooled_at_hand) m = r.pool(in, 0, 2);
+        Act out = efd(r, p, in, &m);
+        if (r.ok() && !r.dry) r.check(launch_to_ncdhw(precision, out.p, y, B, Cout, N, H / 2, W / 2, r.s), "to_ncdhw");
+    });
 }
 
 int dffw_op_regress(int device, const float *score, int B, int N, int h, int w, int H, int W, const float *focus_dists,

@@ -73,6 +73,9 @@ def _load():
                                       POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
                                       POINTER(c_float), POINTER(c_float), c_void_p, c_int, c_void_p, c_void_p, POINTER(c_float), c_void_p, c_void_p]
     lib.dffw_op_pool.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.dffw_op_srd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 6 + [c_void_p] * 3
+    lib.dffw_op_efd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 4 + [c_int, c_void_p, c_void_p]
+    lib.dffw_last_op_kernels.restype = c_char_p
     lib.dffw_op_fov_warp.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_void_p]
     lib.dffw_op_regress.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
@@ -107,7 +110,7 @@ ABI_SYMBOLS = (
     "dffw_version", "dffw_last_error", "dffw_param_count", "dffw_param_info", "dffw_engine_create",
     "dffw_engine_destroy", "dffw_engine_precision", "dffw_workspace_bytes", "dffw_forward",
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
-    "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel",
+    "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
     "dffw_forward_raw", "dffw_pack_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
@@ -301,7 +304,8 @@ class Engine:
 def _tap_shapes(B, N, H, W):
     return {
         "head3": (B, 3, N), "head2": (B, 3, N), "head1": (B, 3, N), "alpha": (B, 3, N),
-        "V1": (B, 8, N, H, W), "V2": (B, 16, N, H // 2, W // 2), "V3": (B, 32, N, H // 4, W // 4),
+        "stem": (B, 8, N, H, W), "V1": (B, 8, N, H, W), "E1": (B, 16, N, H // 2, W // 2), "V2": (B, 16, N, H // 2, W // 2),
+        "E2": (B, 32, N, H // 4, W // 4), "V3": (B, 32, N, H // 4, W // 4),
         "FS_volume": (B, 32, N, H // 8, W // 8), "conf": (B, N, H // 8, W // 8),
         "cost1": (B, N, H // 4, W // 4), "cost2": (B, N, H // 2, W // 2), "cost3": (B, N, H, W),
     }
@@ -367,6 +371,50 @@ def probe_peaks(device=0):
 def last_conv_kernel():
     """Kernel instantiation used by this thread's most recent convolution launch (rocprofv3 spelling)."""
     return lib.dffw_last_conv_kernel().decode()
+
+
+def _host_f32(t):
+    return t.detach().to("cpu", torch.float32).contiguous()
+
+
+def _bn_host(bn):
+    return torch.cat([_host_f32(t).reshape(-1) for t in bn]).contiguous()
+
+
+def op_srd(x, w0, bn0, w2, bn2, w3, w1, *, pooled=False, precision="bf16x3"):
+    """One SRD block (dffw_op_srd) through the forward's dispatch: ``x`` (B,C,N,H,W) float32 on the GPU, C = 8, 16 or 32; the
+    weights in PyTorch layout, ``bn0`` / ``bn2`` = (gamma, beta, mean, var).  Returns y, or (y, max_pool(1,2,2)(y)) with
+    ``pooled``.  op_kernels() then lists the launches."""
+    B, C, N, H, W = x.shape
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    pl = torch.empty((B, C, N, H // 2, W // 2), dtype=torch.float32, device=x.device) if pooled else None
+    host = [_host_f32(w0), _bn_host(bn0), _host_f32(w2), _bn_host(bn2), _host_f32(w3), _host_f32(w1)]
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_srd(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, *[_f32(t) for t in host],
+                               c_void_p(y.data_ptr()), c_void_p(pl.data_ptr()) if pooled else None, _stream_ptr(dev)), "dffw_op_srd")
+    return (y, pl) if pooled else y
+
+
+def op_efd(x, ws, bns, wp, bnp, *, pooled_at_hand=True, precision="bf16x3"):
+    """One EFD block (dffw_op_efd): ``x`` (B,Cin,N,H,W), Cin = 8 or 16, H and W even; returns (B,2*Cin,N,H/2,W/2).  With
+    ``pooled_at_hand`` the pooled copy of x is made first and handed to the block, as in the forward."""
+    B, C, N, H, W = x.shape
+    x = x.contiguous()
+    y = torch.empty((B, 2 * C, N, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    host = [_host_f32(ws), _bn_host(bns), _host_f32(wp), _bn_host(bnp)]
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_efd(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, *[_f32(t) for t in host],
+                               int(bool(pooled_at_hand)), c_void_p(y.data_ptr()), _stream_ptr(dev)), "dffw_op_efd")
+    return y
+
+
+def op_kernels():
+    """Kernel names of every launch of this thread's last op_srd / op_efd call, in launch order."""
+    s = lib.dffw_last_op_kernels().decode()
+    return s.split(";") if s else []
 
 
 def op_pool(x, k, mode="max", precision="bf16x3"):

@@ -50,7 +50,8 @@ typedef struct dffw_tensor {
 
 /* Optional debug tap: after the forward, the named intermediate volume is written to `dst`
  * (device, fp32, reference layout (B,C,N,h,w), or (B,N,h,w) for the 1-channel score volumes).
- * Names: V1 V2 V3 FS_volume conf cost1 cost2 cost3; for dffw_forward_e2e also
+ * Names: V1 V2 V3 FS_volume conf cost1 cost2 cost3, stem (the stem conv's output, the
+ * first SRD block's input), E1 E2 (the two EFD blocks' outputs, the inputs of the 16 and 32 channel SRD blocks); for dffw_forward_e2e also
  * head3 head2 head1 (each alpha head's output before the 0.001 damping, (B,3,N)) and alpha (the accumulated
  * warp parameters the stack is finally warped with, (B,3,N)). */
 typedef struct dffw_tap {
@@ -160,6 +161,28 @@ int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin,
 
 int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int B, int C, int N,
                  int H, int W, float *y, void *hip_stream);
+
+/* One SRD block of the front end (DEN.py:317-330: feat = relu(x + BN(conv(relu(BN(conv(x)))))), y = feat +
+ * relu(conv1x1x1(relu(conv3x1x1(feat))))) through the forward's own dispatch, C = 8, 16 or 32 (FM_measure.Focus_extraction.2,
+ * FM_conv1.1, FM_conv2.1).  Test-only.  x, y: device fp32 (B,C,N,H,W).  w0, w2: host fp32 (C,C,1,3,3) with bn0, bn2 (4*C
+ * values gamma|beta|mean|var); w3 (C,C,3,1,1), w1 (C,C,1,1,1).  pooled: device fp32 (B,C,N,H/2,W/2) or NULL: max_pool(1,2,2)
+ * of y, from the fused kernel's side output where that path writes one, else from the pool kernel. */
+int dffw_op_srd(int device, int precision, const float *x, int B, int C, int N, int H, int W,
+                const float *w0, const float *bn0, const float *w2, const float *bn2, const float *w3,
+                const float *w1, float *y, float *pooled, void *hip_stream);
+
+/* One EFD block (DEN.py:306-315: y = relu(BN(conv3^3 s(1,2,2)(x)) + BN(conv3^3(maxpool(1,2,2)(x))))), Cin = 8 or 16,
+ * Cout = 2*Cin (FM_conv1.0, FM_conv2.0), through the forward's own dispatch.  Test-only.  x: device fp32 (B,Cin,N,H,W),
+ * H and W even; y: (B,Cout,N,H/2,W/2).  ws, wp: host fp32 (Cout,Cin,3,3,3) with bns, bnp.  pooled_at_hand != 0: x is first
+ * max-pooled by the pool kernel and the copy handed to the block, as the forward's SRD block leaves it (the fused kernels
+ * need it); 0: the block pools for itself. */
+int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N, int H, int W,
+                const float *ws, const float *bns, const float *wp, const float *bnp, int pooled_at_hand,
+                float *y, void *hip_stream);
+
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd call, in launch order, joined by
+ * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
+const char *dffw_last_op_kernels(void);
 
 /* The regression block of DEN.py:86-90: bilinear resize (align_corners=False) of score (B,N,h,w) to
  * (H,W), softplus+1e-6, normalise over N, sum_N focus_dists*p -> depth (B,H,W).  All device fp32. */

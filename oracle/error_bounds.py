@@ -37,6 +37,37 @@ fp16 subnormals: the fold happens before the cast, so a small ``s_c`` (gamma nea
 the rounding error is absolute, at most half the subnormal spacing 2^-24 per weight: ``2^-25 conv(|x|, 1)``.  A subnormal stored
 result adds at most 2^-25 as well.  Both terms are added to the fp16 bound only.
 
+Fused blocks (srd_ref64, efd_ref64).  The SRD and EFD kernels compute several convs of a block in one launch, keep intermediates in
+LDS (in fp32 or in the storage format) and only the block's output is observable, so their bound composes the per-conv ones.  To
+first order an error ``e`` in a conv's input adds ``|s_c| conv(|e|, |w|)`` to its output (the conv is linear, its folded weights are
+``s_c w``), and ReLU, the residual add and max are 1-Lipschitz, so they pass an error on without growing it.  With every operand
+error bounded by ``alpha`` times its D, the block's D is the sum of each conv's own D (the roundings inside it) and the previous D
+carried through ``|s_c| |w|``:
+
+    SRD  t = relu(BN0(conv(x, w0)))                     D_t    = D(conv0)
+         feat = relu(BN2(conv(t, w2)) + x)              D_feat = D(conv2) + |s2| conv(D_t, |w2|)
+         a = relu(conv(feat, w3))      (3x1x1)          D_a    = D(conv3) + conv(D_feat, |w3|)
+         y = relu(conv(a, w1)) + feat  (1x1x1)          D_y    = D(conv1) + conv(D_a, |w1|) + D_feat
+         pooled = max_pool(1,2,2)(y)                    D_p    = max_pool(D_y) + |pooled|
+    EFD  a = BN_s(conv_s(1,2,2)(x, ws))                 D_a    = D(conv_s)
+         y = relu(BN_p(conv(max_pool(x), wp)) + a)      D_y    = D(conv_p) + D_a
+
+where each ``D(conv)`` is the single-conv scale above evaluated on the float64 reference of its input (its ``|res|`` term holds the
+stored residual's rounding).  Max selects one stored value, so the pooled input of the EFD carries only x's own rounding, which the
+operand term of ``D(conv_p)`` already holds, and ``|max(a) - max(b)| <= max|a - b|`` gives ``max_pool(D_y)`` for the pooled copy (``+ |pooled|``
+for a copy that is rounded once more).  The bound stays ``alpha * D`` with the same alpha: it is linear in the per-conv bounds,
+second-order terms (an error times a rounding) are below 2^-32 for split-bf16 and covered by the margin of the worst-case alpha for
+the 16-bit formats.  The fp16 subnormal term composes the same way.
+
+The carried terms grow by the L1 norm of each filter (``|s_c| sum|w|`` ~ 3 ... 10 at He scale), so through the SRD block's four convs the
+scale reaches some 600 |y|, and a lost lo half of ``feat`` (2^-9 |feat|) would stay under it.  ``srd_ref64(..., prec)`` therefore resolves
+the ReLUs for one arithmetic: where a ReLU's reference input lies below minus that arithmetic's bound of it, the kernel's input is
+negative as well, both outputs are exactly 0 and no error passes; elsewhere the full D passes.  That bound holds for ``prec`` only
+(``Ref64.prec``) and is no longer linear in alpha; without ``prec`` every ReLU passes its input's error on.  Emulated through both blocks (tests/test_error_bounds.py) the worst
+ratio stays under 0.5 in all three arithmetics, slice counts 1, 2, 3 and every regime below (0.44 EFD, 0.35 SRD); a missed residual in one column, a slice
+padding read from the neighbour, ``feat`` kept as hi halves in one strip, a wrong pixel of the pooled window or a pooled branch one
+row off at a tile seam each exceed the bound at least 4x.
+
 Nothing here imports the reference; only torch.
 """
 import torch
@@ -53,6 +84,8 @@ class Ref64:
     """Float64 reference of one conv op: ``ref`` (the op's output), ``pre`` (BN(conv) before residual and ReLU, what the op's
     ``want_pre`` returns), ``D`` (the per-element scale of the bound) and ``sub`` (the fp16 subnormal term, absolute)."""
 
+    prec = None   # the one arithmetic D holds for (a block's bound with its ReLUs resolved, srd_ref64), or None: every one
+
     def __init__(self, ref, pre, D, sub):
         self.ref, self.pre, self.D, self.sub = ref, pre, D, sub
 
@@ -61,6 +94,7 @@ class Ref64:
         return Ref64(self.ref.squeeze(1), self.pre.squeeze(1), self.D.squeeze(1), self.sub.squeeze(1))
 
     def bound(self, prec):
+        assert self.prec in (None, prec), "this bound was composed for %s, not %s" % (self.prec, prec)
         b = ALPHA[prec] * self.D
         if prec == "fp16":
             b = b + self.sub
@@ -231,3 +265,103 @@ def bn_regime(kind, c, seed, conv_mean=0.0):
         return gamma, beta, mean, var
     return (0.5 + torch.rand(c, generator=g), torch.rand(c, generator=g) - 0.5,
             torch.rand(c, generator=g) - 0.5, 0.5 + torch.rand(c, generator=g))
+
+
+# ---- the fused front-end blocks: composed bounds (derivation in the module docstring) ------------------------------------------
+def _carry(D, w, scale=None, pad=0):
+    """``|s_c| conv(D, |w|)``: an input error bounded by D, carried through a conv (its folded weights are s_c * w)."""
+    out = F.conv3d(D, w.detach().cpu().double().abs(), None, 1, pad)
+    return out if scale is None else out * scale.abs().reshape(1, -1, 1, 1, 1)
+
+
+def maxpool_ref64(r):
+    """max_pool(1,2,2) of a block's output (its Ref64): the maximum moves by at most the largest error in the window, and a copy
+    rounded once more adds ``|pooled|``."""
+    ref = F.max_pool3d(r.ref, (1, 2, 2), (1, 2, 2))
+    return Ref64(ref, ref, F.max_pool3d(r.D, (1, 2, 2), (1, 2, 2)) + ref.abs(), F.max_pool3d(r.sub, (1, 2, 2), (1, 2, 2)) + FP16_SUB)
+
+
+def _relu_passes(pre, D, sub, prec):
+    """1 where a ReLU can pass its input's error on, 0 where it cannot: with ``prec`` given, an input whose reference lies below
+    minus that arithmetic's bound is negative in the kernel as well, so both results are exactly 0 there."""
+    if prec is None:
+        return torch.ones_like(pre)
+    return (pre > -Ref64(pre, pre, D, sub).bound(prec)).to(pre.dtype)
+
+
+def srd_ref64(x, w0, bn0, w2, bn2, w3, w1, prec=None):
+    """The SRD block (DEN.py:317-330) in float64: (Ref64 of its output, Ref64 of the max-pooled copy).  ``pre`` of the output is the
+    attention's 1x1x1 conv before its ReLU.  With ``prec`` the four ReLUs pass no error where they are off for certain in that
+    arithmetic (the bound is then that arithmetic's only); without it every ReLU passes its input's error on."""
+    x = x.detach().cpu().double()
+    C = x.shape[1]
+    p2, pa = (0, 1, 1), (1, 0, 0)
+    rt = conv_ref64(x, w0, pad=p2, bn=bn0, relu=1)
+    on = _relu_passes(rt.pre, rt.D, rt.sub, prec)
+    D_t, sub_t = rt.D * on, rt.sub * on
+    s2, _ = fold_bn(bn2, C)
+    rf = conv_ref64(rt.ref, w2, pad=p2, bn=bn2, residual=x, relu=1)
+    D_feat = rf.D + _carry(D_t, w2, s2, p2)
+    sub_feat = rf.sub + _carry(sub_t, w2, s2, p2)
+    on = _relu_passes(rf.pre + x, D_feat, sub_feat, prec)
+    D_feat, sub_feat = D_feat * on, sub_feat * on
+    ra = conv_ref64(rf.ref, w3, pad=pa, relu=1)
+    D_a = ra.D + _carry(D_feat, w3, pad=pa)
+    sub_a = ra.sub + _carry(sub_feat, w3, pad=pa)
+    on = _relu_passes(ra.pre, D_a, sub_a, prec)
+    D_a, sub_a = D_a * on, sub_a * on
+    ro = conv_ref64(ra.ref, w1, residual=rf.ref, relu=2)
+    D_1, sub_1 = ro.D - rf.ref.abs() + _carry(D_a, w1), ro.sub + _carry(sub_a, w1)   # the 1x1x1 conv before its ReLU ...
+    on = _relu_passes(ro.pre, D_1, sub_1, prec)
+    # ... then + feat (its storage rounding: |feat|), and the sum stored once more (|y| <= |relu(pre)| + |feat|; a subnormal: FP16_SUB)
+    out = Ref64(ro.ref, ro.pre, D_1 * on + rf.ref.abs() + D_feat, sub_1 * on + sub_feat + FP16_SUB)
+    out.prec = prec
+    pooled = maxpool_ref64(out)
+    pooled.prec = prec
+    return out, pooled
+
+
+def efd_ref64(x, ws, bns, wp, bnp):
+    """The EFD block (DEN.py:306-315) in float64: relu(BN_s(conv s(1,2,2)(x)) + BN_p(conv(max_pool(x)))), a Ref64 whose ``pre`` is
+    the pooled branch's BN(conv)."""
+    x = x.detach().cpu().double()
+    ra = conv_ref64(x, ws, stride=(1, 2, 2), pad=1, bn=bns)
+    rb = conv_ref64(F.max_pool3d(x, (1, 2, 2), (1, 2, 2)), wp, pad=1, bn=bnp, residual=ra.ref, relu=1)
+    return Ref64(rb.ref, rb.pre, rb.D + ra.D, rb.sub + ra.sub)
+
+
+def _block_weight(shape, K, g, bn):
+    """Uniform weights of rms ~ sqrt(2 / K) * 1.7 / sqrt(3); with a BatchNorm whose scale |s_c| exceeds 4 (var down to 1e-4) the
+    weights are divided by max|s_c| / 4, so that two such convs in a row stay well inside the fp16 range while the per-channel
+    scales keep their spread (folded weights of the small-scale channels then land in the fp16 subnormals)."""
+    w = (torch.rand(*shape, generator=g) * 2 - 1) * (2.0 / K) ** 0.5 * 1.7
+    if bn is not None:
+        s, _ = fold_bn(bn, shape[0])
+        w = w / max(1.0, float(s.abs().max()) / 4)
+    return w
+
+
+def srd_params(kind, C, seed):
+    """Weights of one SRD block in a regime (see REGIMES): (w0, bn0, w2, bn2, w3, w1); both BatchNorms from bn_regime."""
+    g = torch.Generator().manual_seed(seed)
+    bn0, bn2 = bn_regime(kind, C, seed + 1), bn_regime(kind, C, seed + 2)
+    w0 = _block_weight((C, C, 1, 3, 3), 9 * C, g, bn0)
+    w2 = _block_weight((C, C, 1, 3, 3), 9 * C, g, bn2)
+    w3 = _block_weight((C, C, 3, 1, 1), 3 * C, g, None)
+    w1 = _block_weight((C, C, 1, 1, 1), C, g, None)
+    if kind == "offset":    # the first BN centred on what the input's common offset 3 gives (heavy cancellation, as in make_case)
+        bn0 = bn_regime(kind, C, seed + 1, conv_mean=3.0 * float(w0.double().sum() / C))
+    return w0, bn0, w2, bn2, w3, w1
+
+
+def efd_params(kind, cin, seed):
+    """Weights of one EFD block cin -> 2 cin in a regime: (ws, bns, wp, bnp)."""
+    g = torch.Generator().manual_seed(seed)
+    cout = 2 * cin
+    bns, bnp = bn_regime(kind, cout, seed + 1), bn_regime(kind, cout, seed + 2)
+    ws = _block_weight((cout, cin, 3, 3, 3), 27 * cin, g, bns)
+    wp = _block_weight((cout, cin, 3, 3, 3), 27 * cin, g, bnp)
+    if kind == "offset":    # both branches centred: their sum then cancels twice
+        bns = bn_regime(kind, cout, seed + 1, conv_mean=3.0 * float(ws.double().sum() / cout))
+        bnp = bn_regime(kind, cout, seed + 2, conv_mean=3.0 * float(wp.double().sum() / cout))
+    return ws, bns, wp, bnp

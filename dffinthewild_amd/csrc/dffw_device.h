@@ -460,6 +460,30 @@ __device__ __forceinline__ WarpPoint warp_point(int xx, int yy, int H, int W, fl
 }
 
 
+// The focal-stack simulator's warp (Simulator/synthetic_blur_movement.py:15-66, FOV_warp / DepthFOV_warp): a different operation
+// order from warp_point above, all float32 as torch CPU evaluates it.  torch.linspace on the CPU is computed with a fused multiply-add
+// (start + step*i below the half-way index, end - step*(steps-1-i) from it); (FoV - 1) enters as a scalar rounded to float32 once;
+// every other step is its own torch operation, so nothing else is fused.  (sx, sy): the source pixel position grid_sample
+// (align_corners=True) unnormalises to, (g + 1) * ((size - 1) / 2).  Needs H, W >= 2.
+struct SimWarpPoint {
+    float sx, sy;
+};
+__device__ __forceinline__ SimWarpPoint sim_warp_point(int xx, int yy, int H, int W, float fm1, float beta, float gamma) {
+#pragma clang fp contract(off)
+    const float stepx = 2.0f / (float)(W - 1), stepy = 2.0f / (float)(H - 1);
+    const float lx = xx < W / 2 ? fmaf(stepx, (float)xx, -1.0f) : fmaf(-stepx, (float)(W - 1 - xx), 1.0f);
+    const float ly = yy < H / 2 ? fmaf(stepy, (float)yy, -1.0f) : fmaf(-stepy, (float)(H - 1 - yy), 1.0f);
+    const float g2x = (float)(W / 2) * (fm1 * lx) - beta;    // ((W//2)*((Fov-1)*lin)) - beta
+    const float g2y = (float)(H / 2) * (fm1 * ly) - gamma;
+    const float gx = 2.0f * ((float)xx - g2x) / (float)(W - 1) - 1.0f;
+    const float gy = 2.0f * ((float)yy - g2y) / (float)(H - 1) - 1.0f;
+    SimWarpPoint p;
+    p.sx = (gx + 1.0f) * ((float)(W - 1) / 2.0f);
+    p.sy = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
+    return p;
+}
+
+
 // bilinear sample (zeros outside, grid_sample align_corners=True) of 8 consecutive channels of a channels-last slice at the
 // warped position of `wp`; `slice` points at channel octet's first element of pixel (0,0).  v must be zero-initialised.
 template <int PREC>

@@ -49,6 +49,7 @@ int dffw_fail(int code, const char *fmt, ...) {
     dffw::g_err = buf;
     return code;
 }
+void dffw_set_last_op_kernels(const char *names) { dffw::g_last_op_kernels = names ? names : ""; }
 namespace dffw {
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \

@@ -5,6 +5,8 @@
 
 // thread-local error message of the C ABI (dffw_last_error); returns `code`
 int dffw_fail(int code, const char *fmt, ...);
+// sets dffw_last_op_kernels() of the calling thread (';'-joined kernel names) for entry points outside dffw_engine.cpp
+void dffw_set_last_op_kernels(const char *names);
 
 namespace dffw {
 

@@ -38,6 +38,12 @@ class _Prof(ctypes.Structure):
                 ("ms", c_float)]
 
 
+class SimParams(ctypes.Structure):
+    """dffw_sim_params (include/dffw.h)."""
+    _fields_ = [("pixel_per_meter", ctypes.c_double), ("min_depth", ctypes.c_double), ("max_depth", ctypes.c_double),
+                ("min_focus", ctypes.c_double), ("max_focus", ctypes.c_double), ("num_planes", c_int), ("max_radius", c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise DffwError(
@@ -98,6 +104,12 @@ def _load():
     lib.dffw_comm_size.argtypes = [c_void_p]
     lib.dffw_allgather.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_probe_peaks.argtypes = [c_int, POINTER(c_float), POINTER(c_float), c_void_p]
+    lib.dffw_sim_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.dffw_sim_workspace_bytes.restype = c_int64
+    lib.dffw_sim_render.argtypes = [c_int, SimParams, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]
+    lib.dffw_sim_plan_host.argtypes = [POINTER(SimParams), POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, c_int,
+                                       POINTER(ctypes.c_double), POINTER(c_int), POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int)]
+    lib.dffw_sim_disk_rows.argtypes = [c_int, POINTER(c_int)]
     return lib
 
 
@@ -114,6 +126,7 @@ ABI_SYMBOLS = (
     "dffw_forward_raw", "dffw_pack_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
+    "dffw_sim_workspace_bytes", "dffw_sim_render", "dffw_sim_plan_host", "dffw_sim_disk_rows",
 )
 
 
@@ -456,3 +469,81 @@ def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False):
                                     int(compat_batch_alpha0), c_void_p(out.data_ptr()), c_void_p(flow.data_ptr()),
                                     _stream_ptr(dev)), "dffw_op_fov_warp")
     return out, flow
+
+
+# ---- focal-stack simulator (dffw_sim_*) --------------------------------------------------------------------------------------
+SIM_LDS_RADIUS = 32     # DFFW_SIM_LDS_RADIUS
+SIM_NSCALARS = 12       # DFFW_SIM_NSCALARS, in this order:
+SIM_SCALARS = ("fd", "fd_px", "lens_to_sensor", "fov", "coc_scale", "f_px", "lens_dia", "scene_min", "scene_max", "min_afov",
+               "max_afov", "origin_max_afov")
+
+
+def sim_params(pixel_per_meter, depth_range, focus_range, num_planes, max_radius=-1):
+    """dffw_sim_params from (min_depth, max_depth) and (min_focus, max_focus)."""
+    return SimParams(float(pixel_per_meter), float(depth_range[0]), float(depth_range[1]), float(focus_range[0]),
+                     float(focus_range[1]), int(num_planes), int(max_radius))
+
+
+def sim_plan_host(params, cam, dmin, dmax, N):
+    """dffw_sim_plan_host: per-slice scalars (N, SIM_NSCALARS) and the layer tables [(coc, lo, hi) arrays] of every slice."""
+    import numpy as np
+    P = params.num_planes
+    sc = np.zeros((N, SIM_NSCALARS), np.float64)
+    coc = np.zeros((N, P), np.int32)
+    lo = np.zeros((N, P), np.float64)
+    hi = np.zeros((N, P), np.float64)
+    nl = np.zeros(N, np.int32)
+    dp = POINTER(ctypes.c_double)
+    camv = (ctypes.c_double * 4)(*[float(v) for v in cam])
+    _check(lib.dffw_sim_plan_host(byref(params), camv, float(dmin), float(dmax), N, sc.ctypes.data_as(dp),
+                                  coc.ctypes.data_as(POINTER(c_int)), lo.ctypes.data_as(dp), hi.ctypes.data_as(dp),
+                                  nl.ctypes.data_as(POINTER(c_int))), "dffw_sim_plan_host")
+    return sc, [(coc[n, :nl[n]].copy(), lo[n, :nl[n]].copy(), hi[n, :nl[n]].copy()) for n in range(N)]
+
+
+def sim_disk_rows(r):
+    """dffw_sim_disk_rows: half-widths of rows 0..r of the radius-r disk, and the tap count K."""
+    hw = (c_int * (r + 1))()
+    K = _check(lib.dffw_sim_disk_rows(r, hw), "dffw_sim_disk_rows")
+    return list(hw), K
+
+
+def op_sim_render(image, depth, cams, shifts, params, *, tap=False, workspace=None):
+    """dffw_sim_render on the GPU.  image float32 (B,H,W,3) 0..255, depth float64 (B,H,W), cams float64 (B,4), shifts float64
+    (B,N,2), all CUDA tensors on one device; params a SimParams.  Returns a dict: images uint8 (B,N,H,W,3), defocus float64
+    (B,N,H,W), depth float32 (B,H,W), status int32 (B), slices float64 (B,N,2) (focus distance, FoV), and with ``tap`` the
+    warped float image (B,N,H,W,3).  ``workspace``: optional uint8 CUDA tensor of at least sim_workspace_bytes bytes.
+    op_kernels() then lists the launches."""
+    B, H, W, C = image.shape
+    N = shifts.shape[1]
+    if C != 3 or tuple(depth.shape) != (B, H, W) or tuple(cams.shape) != (B, 4) or tuple(shifts.shape) != (B, N, 2):
+        raise ValueError(f"shapes image {tuple(image.shape)} depth {tuple(depth.shape)} cams {tuple(cams.shape)} shifts {tuple(shifts.shape)}")
+    if image.dtype != torch.float32 or depth.dtype != torch.float64 or cams.dtype != torch.float64 or shifts.dtype != torch.float64:
+        raise TypeError("image float32, depth / cams / shifts float64")
+    dev = image.device
+    if dev.type != "cuda" or any(t.device != dev for t in (depth, cams, shifts)):
+        raise DffwError("the simulator runs on one GPU: every input must be a CUDA tensor on the same device")
+    image, depth, cams, shifts = (t.contiguous() for t in (image, depth, cams, shifts))
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    need = lib.dffw_sim_workspace_bytes(B, N, H, W, params.num_planes)
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+    out = {
+        "images": torch.empty((B, N, H, W, 3), dtype=torch.uint8, device=dev),
+        "defocus": torch.empty((B, N, H, W), dtype=torch.float64, device=dev),
+        "depth": torch.empty((B, H, W), dtype=torch.float32, device=dev),
+        "status": torch.empty((B,), dtype=torch.int32, device=dev),
+        "slices": torch.empty((B, N, 2), dtype=torch.float64, device=dev),
+    }
+    if tap:
+        out["warped"] = torch.empty((B, N, H, W, 3), dtype=torch.float32, device=dev)
+    ptr = lambda k: c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
+    with torch.cuda.device(idx):
+        _check(lib.dffw_sim_render(idx, params, c_void_p(cams.data_ptr()), c_void_p(image.data_ptr()), c_void_p(depth.data_ptr()),
+                                   c_void_p(shifts.data_ptr()), B, N, H, W, ptr("images"), ptr("defocus"), ptr("depth"), ptr("status"),
+                                   ptr("slices"), ptr("warped"), c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(idx)),
+               "dffw_sim_render")
+    return out
+
+
+def sim_workspace_bytes(B, N, H, W, num_planes):
+    return int(lib.dffw_sim_workspace_bytes(B, N, H, W, num_planes))

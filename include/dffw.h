@@ -180,7 +180,7 @@ int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N
                 const float *ws, const float *bns, const float *wp, const float *bnp, int pooled_at_hand,
                 float *y, void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd call, in launch order, joined by
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_sim_render call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 
@@ -265,6 +265,58 @@ int dffw_unpack_stack(int device, const float *warp, int B, int N, int H, int W,
 int64_t dffw_metrics_scratch_bytes(int B);
 int dffw_metrics(int device, const float *est, int B, int H, int W, const float *gt, const uint8_t *mask,
                  const float *conf, int h, int w, double *out, void *scratch, int64_t scratch_bytes, void *hip_stream);
+
+/* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
+ * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
+ * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is
+ * warped by its field of view and a (beta, gamma) pixel shift; every pixel is blurred by the disk of its depth layer's
+ * circle of confusion.  DESIGN.md §10 states the arithmetic contract (all float64 scalars and layer tables
+ * as Python evaluates them; the warp as torch CPU float32; the disk blur as an exact integer sum rounded to nearest).
+ * The defocus map follows NumPy >= 2 promotion (NEP 50): for n >= 1 the float32 warped depth meets the float64 focus distance
+ * in float64 (the reference's pinned NumPy 1.21 would have computed it in float32).  Warped-out pixels give inf, as there. */
+typedef struct dffw_sim_params {
+    double pixel_per_meter;        /* args.pixel_vs_meter */
+    double min_depth, max_depth;   /* depth normalisation: d' = max_depth*(d - min d)/(max d - min d) + min_depth */
+    double min_focus, max_focus;   /* focus range in metres (the reference fixes 0.1, 0.9) */
+    int num_planes;                /* depth planes scanned for the CoC layer table (args.num_planes) */
+    int max_radius;                /* upper bound of every blur radius, or -1 if unknown.  Steers speed only: above
+                                    * DFFW_SIM_LDS_RADIUS the global-memory kernel is launched; a tile whose radius exceeds
+                                    * the LDS halo reads global memory in either kernel. */
+} dffw_sim_params;
+#define DFFW_SIM_LDS_RADIUS 32     /* largest blur radius the render kernel stages in LDS */
+#define DFFW_SIM_DISCARD 1         /* status bit 0: the warped depth has a 0 minimum; the reference drops the sample (:274) */
+/* per-slice scalars of dffw_sim_plan_host, in this order (FoV is 1 for slice 0, which is not warped) */
+#define DFFW_SIM_NSCALARS 12
+enum { DFFW_SIM_FD, DFFW_SIM_FD_PX, DFFW_SIM_LENS_TO_SENSOR, DFFW_SIM_FOV, DFFW_SIM_COC_SCALE, DFFW_SIM_F_PX, DFFW_SIM_LENS_DIA,
+       DFFW_SIM_SCENE_MIN, DFFW_SIM_SCENE_MAX, DFFW_SIM_MIN_AFOV, DFFW_SIM_MAX_AFOV, DFFW_SIM_ORIGIN_MAX_AFOV };
+
+/* Bytes of workspace dffw_sim_render needs. */
+int64_t dffw_sim_workspace_bytes(int B, int N, int H, int W, int num_planes);
+
+/* Enqueue-only on hip_stream; every pointer is device memory.
+ *   cams       fp64 (B,4): focal length (m), F-number, alpha slope, alpha intercept of sample b's camera
+ *   image      fp32 (B,H,W,3), 0..255, channel order as cv2 reads it
+ *   depth      fp64 (B,H,W) raw depth (normalised inside; a constant map is outside the contract)
+ *   shifts     fp64 (B,N,2) beta, gamma in pixels (already scaled by the size ratio); slice 0's entry is ignored
+ *   images     uint8 (B,N,H,W,3): the blurred slices, channels reversed (the array the reference hands to imwrite)
+ *   defocus    fp64 (B,N,H,W): |coc_scale*(d_px - fd_px)/d_px|
+ *   depth_out  fp32 (B,H,W): normalised depth warped by the last slice's FoV and shift
+ *   status     int32 (B): DFFW_SIM_DISCARD bits
+ *   slices     fp64 (B,N,2) or NULL: focus distance (m) and FoV of every slice
+ *   warped_tap fp32 (B,N,H,W,3) or NULL: the warped float image before the uint8 truncation (debug tap)
+ * N >= 2, H, W >= 2, num_planes >= 1.  dffw_last_op_kernels() lists the launches. */
+int dffw_sim_render(int device, dffw_sim_params params, const double *cams, const float *image, const double *depth,
+                    const double *shifts, int B, int N, int H, int W, uint8_t *images, double *defocus, float *depth_out,
+                    int32_t *status, double *slices, float *warped_tap, void *workspace, int64_t ws_bytes, void *hip_stream);
+
+/* The same per-slice scalars and CoC layer tables on the CPU, from one camera and the raw depth's (min, max): scalars
+ * (N, DFFW_SIM_NSCALARS); coc / lo / hi (N, num_planes), layer i of slice n = [lo, hi) blurred with radius |coc| (0 -> 1);
+ * nlayers (N).  The device's plan kernel runs the same function. */
+int dffw_sim_plan_host(const dffw_sim_params *params, const double cam[4], double dmin, double dmax, int N, double *scalars,
+                       int *coc, double *lo, double *hi, int *nlayers);
+
+/* Half-widths of the rows 0..r of the radius-r disk (cv2.circle filled, restated in DESIGN.md); returns the tap count K. */
+int dffw_sim_disk_rows(int r, int *halfwidths);
 
 /* ---- measured ceilings of the GPU at hand (bench.py prints them beside the datasheet peaks) -------------------------------
  * mfma_tflops: v_mfma_f32_16x16x32_bf16 issued back to back out of registers on every SIMD (no memory traffic);

@@ -51,6 +51,7 @@ class Network(_DepthNetwork):
 
     def forward_with_taps(self, FS, focus_dists, FOVs, names):
         """Debug variant: also returns {name: tensor} — head3, head2, head1 (each alpha head before damping) and
-        alpha, all (B,3,N), plus the DFF_net taps of the depth module."""
+        alpha, all (B,3,N), alpha3 / alpha2 (after the level-3 / level-2 heads), fe1 / fe2 / fe3 (the three feature
+        levels), plus the DFF_net taps of the depth module."""
         FS, focus_dists, FOVs = self._check_e2e(FS, focus_dists, FOVs)
         return self._engine_on(FS.device).forward_e2e(FS, focus_dists, FOVs, taps=list(names))

@@ -1906,6 +1906,53 @@ static Act of_block(Run &r, const std::string &p, const Act &x) {
     return out;
 }
 
+// The first feature block (OF_feature.0, End_to_End.py:72) from the fp32 stack FS (B,3,N,H,W): of_first_kernel reads the stack itself
+// when its streaming form applies (of_roll8 with the record conversion inside its fill: the 8-channel record volume of the stack is
+// neither written nor read), else the stack is converted to an 8-channel record volume and of_block() takes it.
+static Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W) {
+    const int prec = r.e->prec;
+    Act a0;
+    auto c0 = r.e->convs.find(p0 + ".conv.0.0"), c2 = r.e->convs.find(p0 + ".conv.2.0");
+    const auto end = r.e->convs.end();
+    const bool first = c0 != end && c2 != end && r.e->convs.find(p0 + ".feature") == end && c0->second.wsrd && c2->second.wsrd &&
+                       c0->second.def.cin == 3 && c0->second.def.cout == 8 && c2->second.def.cout == 8 && c2->second.cin_all == 16 && H % 8 == 0 &&
+                       W % 16 == 0 && (int64_t)B * (H / 8) * (W / 16) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_OF_FIRST) &&
+                       !r.sw.on(SW_NO_TILE);
+    if (first) {
+        a0 = r.act(B, N, H, W, 8);
+        if (r.ok() && !r.dry) {
+            SrdArgs a;
+            memset(&a, 0, sizeof a);
+            a.w3 = FS; a.out = a0.p;
+            a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd;
+            a.b0 = c0->second.bias; a.b2 = c2->second.bias;
+            a.B = B; a.N = N; a.H = H; a.W = W;
+            a.tiles_y = H / 8; a.tiles_x = W / 16;
+            a.total_tiles = B * a.tiles_y * a.tiles_x;
+            a.wgs = r.sw.srd_wgs;
+            char kn[64];
+            of_first_kernel_name(prec, kn, sizeof kn);
+            g_last_kernel = kn;
+            const double px = (double)B * N * H * W;
+            r.prof_begin(kn, p0, 2.0 * px * (9.0 * 3 * 8 + 9.0 * 8 * 8 + 3.0 * 8), px * (3 * 4.0 + 8 * r.elem_bytes()));
+            r.check(launch_of_first(prec, a, r.s), "of_first");
+            r.prof_end();
+        }
+    } else {
+        Act in = r.act(B, N, H, W, 8);
+        if (r.ok() && !r.dry) {
+            char kn[56];
+            snprintf(kn, sizeof kn, "dffw::from_ncdhw_pad_kernel<%d>", prec);
+            r.prof_begin(kn, "flow.stack_in", 0.0, (double)B * N * H * W * (3 * 4.0 + 8 * r.elem_bytes()));
+            r.check(launch_from_ncdhw_pad(prec, FS, in.p, B, 3, 8, N, H, W, r.s), "from_ncdhw_pad");
+            r.prof_end();
+        }
+        a0 = of_block(r, p0, in);
+        r.drop(in);
+    }
+    return a0;
+}
+
 // End_to_End.Network.forward (End_to_End.py:13-16): FlowNetwork.forward (End_to_End.py:71-105) aligns the stack,
 // DFF_net runs on the aligned stack.  `aligned` receives the warped focal stack (the 5th return value).
 static int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W,
@@ -1914,66 +1961,26 @@ static int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4
     const int prec = r.e->prec;
     ConvOpt rl; rl.relu = 1;
     // three feature levels: full, 1/2, 1/4 resolution                               End_to_End.py:72-74
-    Act a0;
-    {
-        // the first block reads the fp32 stack itself when its streaming kernel applies (of_first_kernel = of_roll8 with the record
-        // conversion inside its fill): the 8-channel record volume of the stack is neither written nor read
-        const std::string p0 = P + ".OF_feature.0";
-        auto c0 = r.e->convs.find(p0 + ".conv.0.0"), c2 = r.e->convs.find(p0 + ".conv.2.0");
-        const auto end = r.e->convs.end();
-        const bool first = c0 != end && c2 != end && r.e->convs.find(p0 + ".feature") == end && c0->second.wsrd && c2->second.wsrd &&
-                           c0->second.def.cin == 3 && c0->second.def.cout == 8 && c2->second.def.cout == 8 && c2->second.cin_all == 16 && H % 8 == 0 &&
-                           W % 16 == 0 && (int64_t)B * (H / 8) * (W / 16) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_OF_FIRST) &&
-                           !r.sw.on(SW_NO_TILE);
-        if (first) {
-            a0 = r.act(B, N, H, W, 8);
-            if (r.ok() && !r.dry) {
-                SrdArgs a;
-                memset(&a, 0, sizeof a);
-                a.w3 = FS; a.out = a0.p;
-                a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd;
-                a.b0 = c0->second.bias; a.b2 = c2->second.bias;
-                a.B = B; a.N = N; a.H = H; a.W = W;
-                a.tiles_y = H / 8; a.tiles_x = W / 16;
-                a.total_tiles = B * a.tiles_y * a.tiles_x;
-                a.wgs = r.sw.srd_wgs;
-                char kn[64];
-                of_first_kernel_name(prec, kn, sizeof kn);
-                g_last_kernel = kn;
-                const double px = (double)B * N * H * W;
-                r.prof_begin(kn, p0, 2.0 * px * (9.0 * 3 * 8 + 9.0 * 8 * 8 + 3.0 * 8), px * (3 * 4.0 + 8 * r.elem_bytes()));
-                r.check(launch_of_first(prec, a, r.s), "of_first");
-                r.prof_end();
-            }
-        } else {
-            Act in = r.act(B, N, H, W, 8);
-            if (r.ok() && !r.dry) {
-                char kn[56];
-                snprintf(kn, sizeof kn, "dffw::from_ncdhw_pad_kernel<%d>", prec);
-                r.prof_begin(kn, "flow.stack_in", 0.0, (double)B * N * H * W * (3 * 4.0 + 8 * r.elem_bytes()));
-                r.check(launch_from_ncdhw_pad(prec, FS, in.p, B, 3, 8, N, H, W, r.s), "from_ncdhw_pad");
-                r.prof_end();
-            }
-            a0 = of_block(r, p0, in);
-            r.drop(in);
-        }
-    }
+    Act a0 = of_first_block(r, P + ".OF_feature.0", FS, B, N, H, W);
     Act fe1 = of_block(r, P + ".OF_feature.1", a0);
     r.drop(a0);
+    r.tap("fe1", fe1);
     Act a1 = of_block(r, P + ".OF_feature1.0", fe1);
     Act fe2 = of_block(r, P + ".OF_feature1.1", a1);
     r.drop(a1);
+    r.tap("fe2", fe2);
     Act a2 = of_block(r, P + ".OF_feature2.0", fe2);
     Act fe3 = of_block(r, P + ".OF_feature2.1", a2);
     r.drop(a2);
+    r.tap("fe3", fe3);
 
     const int64_t na = (int64_t)B * 3 * N;
     float *alpha = (float *)r.raw(na * sizeof(float));   // accumulated (scale offset, x shift, y shift) per (b, slice)
     float *rawh = (float *)r.raw(na * sizeof(float));    // last head output before damping (debug tap)
     if (r.ok() && !r.dry) r.check(hipMemsetAsync(alpha, 0, na * sizeof(float), r.s), "alpha memset");
 
-    struct Level { Act *fe; const char *head; const char *tap; };
-    Level levels[3] = {{&fe3, ".conv1", "head3"}, {&fe2, ".conv2", "head2"}, {&fe1, ".conv3", "head1"}};
+    struct Level { Act *fe; const char *head; const char *tap; const char *atap; };
+    Level levels[3] = {{&fe3, ".conv1", "head3", "alpha3"}, {&fe2, ".conv2", "head2", "alpha2"}, {&fe1, ".conv3", "head1", nullptr}};
     for (const Level &lv : levels) {                      // coarse to fine, End_to_End.py:77-103
         Act &fe = *lv.fe;
         const std::string hp = P + lv.head;
@@ -2160,6 +2167,7 @@ static int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4
             r.drop_raw(hf);
         }
         r.tap_f32(lv.tap, rawh, na);
+        if (lv.atap) r.tap_f32(lv.atap, alpha, na);   // (after level 1 it is the final "alpha" below)
     }
     r.tap_f32("alpha", alpha, na);
     if (r.ok() && !r.dry) {                               // End_to_End.py:104
@@ -2622,6 +2630,47 @@ int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N
         if (pooled_at_hand) m = r.pool(in, 0, 2);
         Act out = efd(r, p, in, &m);
         if (r.ok() && !r.dry) r.check(launch_to_ncdhw(precision, out.p, y, B, Cout, N, H / 2, W / 2, r.s), "to_ncdhw");
+    });
+}
+
+int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, int Cout, int stride,
+                     const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y, void *hip_stream) {
+    g_last_op_kernels.clear();
+    if (!x || !w0 || !bn0 || !w2 || !bn2 || !wf || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    static const struct { int cin, cout, s; const char *name; } blocks[] = {
+        {3, 8, 1, "OF_feature.0"}, {8, 8, 1, "OF_feature.1"}, {8, 16, 2, "OF_feature1.0"},
+        {16, 16, 1, "OF_feature1.1"}, {16, 32, 2, "OF_feature2.0"}, {32, 32, 1, "OF_feature2.1"}};
+    const char *name = nullptr;
+    for (const auto &b : blocks)
+        if (b.cin == Cin && b.cout == Cout && b.s == stride) name = b.name;
+    if (!name) return fail(DFFW_EINVAL, "no alignment feature block has (Cin, Cout, stride) = (%d, %d, %d)", Cin, Cout, stride);
+    if (B < 1 || N < 1 || H < 1 || W < 1 || H % stride || W % stride) return fail(DFFW_EINVAL, "bad shape (H and W must be multiples of the stride)");
+    HIPCHK(hipSetDevice(device));
+    const std::string p = std::string("optical_flow_aggregation.") + name;
+    Table t;
+    t.of_block(p, Cin, Cout, stride);
+    dffw_engine eng;
+    eng.device = device;
+    eng.prec = precision;
+    for (const LayerDef &L : t.layers) {   // as dffw_engine_create packs them: a stride-1 block's shortcut folded into conv.2
+        if (L.folded) continue;
+        const bool sc = !L.shortcut.empty();
+        const float *w = L.conv == p + ".conv.0.0" ? w0 : L.conv == p + ".conv.2.0" ? w2 : wf;
+        const float *bn = L.conv == p + ".conv.0.0" ? bn0 : L.conv == p + ".conv.2.0" ? bn2 : nullptr;
+        const int rc = pack_conv(L, precision, w, bn, nullptr, eng.convs[L.conv], sc ? wf : nullptr, sc ? Cin : 0);
+        if (rc) return rc;
+    }
+    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
+        Act out;
+        if (Cin == 3) {
+            out = of_first_block(r, p, x, B, N, H, W);
+        } else {
+            Act in = r.act(B, N, H, W, Cin);
+            if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, r.s), "from_ncdhw");
+            out = of_block(r, p, in);
+        }
+        if (r.ok() && !r.dry) r.check(launch_to_ncdhw(precision, out.p, y, B, Cout, N, H / stride, W / stride, r.s), "to_ncdhw");
     });
 }
 

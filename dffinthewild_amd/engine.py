@@ -81,6 +81,7 @@ def _load():
     lib.dffw_op_pool.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.dffw_op_srd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 6 + [c_void_p] * 3
     lib.dffw_op_efd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 4 + [c_int, c_void_p, c_void_p]
+    lib.dffw_op_of_block.argtypes = [c_int, c_int, c_void_p] + [c_int] * 7 + [POINTER(c_float)] * 5 + [c_void_p] * 2
     lib.dffw_last_op_kernels.restype = c_char_p
     lib.dffw_op_fov_warp.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_void_p]
@@ -123,6 +124,7 @@ ABI_SYMBOLS = (
     "dffw_engine_destroy", "dffw_engine_precision", "dffw_workspace_bytes", "dffw_forward",
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
+    "dffw_op_of_block",
     "dffw_forward_raw", "dffw_pack_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
@@ -317,6 +319,8 @@ class Engine:
 def _tap_shapes(B, N, H, W):
     return {
         "head3": (B, 3, N), "head2": (B, 3, N), "head1": (B, 3, N), "alpha": (B, 3, N),
+        "alpha3": (B, 3, N), "alpha2": (B, 3, N),
+        "fe1": (B, 8, N, H, W), "fe2": (B, 16, N, H // 2, W // 2), "fe3": (B, 32, N, H // 4, W // 4),
         "stem": (B, 8, N, H, W), "V1": (B, 8, N, H, W), "E1": (B, 16, N, H // 2, W // 2), "V2": (B, 16, N, H // 2, W // 2),
         "E2": (B, 32, N, H // 4, W // 4), "V3": (B, 32, N, H // 4, W // 4),
         "FS_volume": (B, 32, N, H // 8, W // 8), "conf": (B, N, H // 8, W // 8),
@@ -424,8 +428,24 @@ def op_efd(x, ws, bns, wp, bnp, *, pooled_at_hand=True, precision="bf16x3"):
     return y
 
 
+def op_of_block(x, w0, bn0, w2, bn2, wf, *, stride=1, precision="bf16x3"):
+    """One resnet_block_2d_OF of the alignment network (dffw_op_of_block) through the forward's dispatch: ``x`` (B,Cin,N,H,W) float32
+    on the GPU (the fp32 stack for the 3 -> 8 first block), weights in PyTorch layout, ``bn0`` / ``bn2`` = (gamma, beta, mean, var),
+    ``wf`` the shortcut's 1x1x1 weights.  Returns (B,Cout,N,H/stride,W/stride).  op_kernels() then lists the launches."""
+    B, C, N, H, W = x.shape
+    Cout = w0.shape[0]
+    x = x.contiguous()
+    y = torch.empty((B, Cout, N, H // stride, W // stride), dtype=torch.float32, device=x.device)
+    host = [_host_f32(w0), _bn_host(bn0), _host_f32(w2), _bn_host(bn2), _host_f32(wf)]
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_of_block(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, Cout, stride,
+                                    *[_f32(t) for t in host], c_void_p(y.data_ptr()), _stream_ptr(dev)), "dffw_op_of_block")
+    return y
+
+
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd call, in launch order."""
+    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
 

@@ -52,8 +52,9 @@ typedef struct dffw_tensor {
  * (device, fp32, reference layout (B,C,N,h,w), or (B,N,h,w) for the 1-channel score volumes).
  * Names: V1 V2 V3 FS_volume conf cost1 cost2 cost3, stem (the stem conv's output, the
  * first SRD block's input), E1 E2 (the two EFD blocks' outputs, the inputs of the 16 and 32 channel SRD blocks); for dffw_forward_e2e also
- * head3 head2 head1 (each alpha head's output before the 0.001 damping, (B,3,N)) and alpha (the accumulated
- * warp parameters the stack is finally warped with, (B,3,N)). */
+ * head3 head2 head1 (each alpha head's output before the 0.001 damping, (B,3,N)), alpha3 alpha2 (the accumulated warp
+ * parameters after the level-3 and level-2 heads, (B,3,N)), alpha (the accumulated warp parameters the stack is finally warped
+ * with, (B,3,N)) and fe1 fe2 fe3 (the alignment network's three feature levels, (B,8,N,H,W), (B,16,N,H/2,W/2), (B,32,N,H/4,W/4)). */
 typedef struct dffw_tap {
     const char *name;
     float *dst;
@@ -180,7 +181,17 @@ int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N
                 const float *ws, const float *bns, const float *wp, const float *bnp, int pooled_at_hand,
                 float *y, void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_sim_render call, in launch order, joined by
+/* One resnet_block_2d_OF of the alignment network (End_to_End.py:135-145: y = relu(feature(x) + BN2(conv(relu(BN0(conv_s(x))))))),
+ * feature a bias-free 1x1x1 conv with the same (1,s,s) stride) through the forward's own dispatch.  Test-only.  (Cin, Cout, stride)
+ * is one of (3,8,1) (8,8,1) (8,16,2) (16,16,1) (16,32,2) (32,32,1) (OF_feature.0 ... OF_feature2.1); for (3,8,1) x is the fp32 stack
+ * and the first block's own dispatch (of_first_kernel, or the padded record volume and the general block) runs.  x: device fp32
+ * (B,Cin,N,H,W), H and W multiples of the stride; y: (B,Cout,N,H/stride,W/stride).  w0: host fp32 (Cout,Cin,1,3,3), w2
+ * (Cout,Cout,1,3,3) with bn0, bn2 (4*Cout values gamma|beta|mean|var); wf (Cout,Cin,1,1,1). */
+int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, int Cout, int stride,
+                     const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y,
+                     void *hip_stream);
+
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_sim_render call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 

@@ -68,6 +68,20 @@ ratio stays under 0.5 in all three arithmetics, slice counts 1, 2, 3 and every r
 padding read from the neighbour, ``feat`` kept as hi halves in one strip, a wrong pixel of the pooled window or a pooled branch one
 row off at a tile seam each exceed the bound at least 4x.
 
+Alignment feature blocks (of_ref64).  resnet_block_2d_OF (End_to_End.py:135-145) is two 1x3x3 convbn and a bias-free 1x1x1 shortcut,
+both first convs with the block's (1,s,s) stride:
+
+         t = relu(BN0(conv_s(x, w0)))                   D_t = D(conv0)
+         f = conv1x1_s(x, wf)                           D_f = conv(|x|, |wf|) + |f|
+         y = relu(BN2(conv(t, w2)) + f)                 D_y = D(conv2) + |s2| conv(D_t, |w2|) + D_f
+
+A stride-1 block folds the shortcut into conv.2's contraction over [t | x] (its products are then rounded like conv.2's own; the
+``conv(|x|, |wf|)`` term covers them and ``|f|`` a stored copy), a stride-2 block adds a stored ``f`` as a residual: one D serves both.
+``of_ref64(..., prec)`` resolves both ReLUs as srd_ref64 does.  The 3 -> 8 first block reads the fp32 stack, rounded once to the
+operand format (the ``|s_c| S`` term).  Emulated through the block (tests/test_error_bounds.py) the worst ratio stays under 0.5 in all
+three arithmetics, every regime and slice counts 1, 2, 3 and 10; the stride-2 shortcut reading the odd pixel, a missed shortcut in one
+column and ``t`` kept as hi halves in one strip each exceed the bound at least 4x.
+
 Nothing here imports the reference; only torch.
 """
 import torch
@@ -365,3 +379,41 @@ def efd_params(kind, cin, seed):
         bns = bn_regime(kind, cout, seed + 1, conv_mean=3.0 * float(ws.double().sum() / cout))
         bnp = bn_regime(kind, cout, seed + 2, conv_mean=3.0 * float(wp.double().sum() / cout))
     return ws, bns, wp, bnp
+
+
+# ---- the alignment network's feature blocks ----------------------------------------------------------------------------------------
+def of_ref64(x, w0, bn0, w2, bn2, wf, stride, prec=None):
+    """resnet_block_2d_OF (End_to_End.py:135-145) in float64: relu(conv1x1_s(x, wf) + BN2(conv(relu(BN0(conv_s(x, w0))), w2))), a Ref64
+    whose ``pre`` is BN2(conv) + shortcut before the last ReLU.  With ``prec`` both ReLUs pass no error where they are off for certain
+    in that arithmetic (see srd_ref64)."""
+    x = x.detach().cpu().double()
+    Cout = w0.shape[0]
+    s, p2 = (1, stride, stride), (0, 1, 1)
+    rt = conv_ref64(x, w0, stride=s, pad=p2, bn=bn0, relu=1)
+    on = _relu_passes(rt.pre, rt.D, rt.sub, prec)
+    D_t, sub_t = rt.D * on, rt.sub * on
+    rf = conv_ref64(x, wf, stride=s)
+    ry = conv_ref64(rt.ref, w2, pad=p2, bn=bn2, residual=rf.ref, relu=1)
+    s2, _ = fold_bn(bn2, Cout)
+    pre = ry.pre + rf.ref
+    D = ry.D + _carry(D_t, w2, s2, p2) + rf.D - rf.ref.abs()   # (ry.D holds |f| already: its residual term)
+    sub = ry.sub + _carry(sub_t, w2, s2, p2) + rf.sub
+    on = _relu_passes(pre, D, sub, prec)
+    out = Ref64(ry.ref, pre, D * on, sub * on)
+    out.prec = prec
+    return out
+
+
+OF_BLOCKS = ((3, 8, 1), (8, 8, 1), (8, 16, 2), (16, 16, 1), (16, 32, 2), (32, 32, 1))   # (Cin, Cout, stride): OF_feature.0 ... OF_feature2.1
+
+
+def of_params(kind, cin, cout, seed):
+    """Weights of one alignment feature block in a regime (see REGIMES): (w0, bn0, w2, bn2, wf)."""
+    g = torch.Generator().manual_seed(seed)
+    bn0, bn2 = bn_regime(kind, cout, seed + 1), bn_regime(kind, cout, seed + 2)
+    w0 = _block_weight((cout, cin, 1, 3, 3), 9 * cin, g, bn0)
+    w2 = _block_weight((cout, cout, 1, 3, 3), 9 * cout, g, bn2)
+    wf = _block_weight((cout, cin, 1, 1, 1), cin, g, None)
+    if kind == "offset":    # the first BN centred on what the input's common offset 3 gives
+        bn0 = bn_regime(kind, cout, seed + 1, conv_mean=3.0 * float(w0.double().sum() / cout))
+    return w0, bn0, w2, bn2, wf

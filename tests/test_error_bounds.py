@@ -422,6 +422,113 @@ def test_block_fault_efd_pooled_branch_one_row_off_at_a_seam(cin, seam, c0, w):
         _record("efd seam row", prec, *_block_fault(bad, good, r, prec))
 
 
+# ---- the alignment network's feature blocks (resnet_block_2d_OF) chained through emulate() ----------------------------------------
+def _emulate_folded(t, x, w2, bn2, wf, prec):
+    """A stride-1 block's conv.2 with the shortcut folded into its contraction, as the packer builds it: one conv over [t | x] whose
+    weights are [s2 * w2 | wf at the centre tap], products of the operand format, fp32 accumulation, shift, ReLU, stored result."""
+    ws2, t2 = fold(w2, bn2, False)
+    wfc = torch.zeros(wf.shape[0], wf.shape[1], 1, 3, 3)
+    wfc[:, :, :, 1, 1] = wf[:, :, :, 0, 0]
+    xc, wc = torch.cat([t, x], 1), torch.cat([ws2, wfc], 1)
+    xh, xl = split(xc, prec)
+    wh, wl = split(wc, prec)
+    acc = _conv32(xh, wh, G_2D)
+    if prec == "bf16x3":
+        acc = acc + _conv32(xh, wl, G_2D) + _conv32(xl, wh, G_2D)
+    return store(F.relu(acc + t2.reshape(1, -1, 1, 1, 1)), prec)
+
+
+def emulate_of(x, w0, bn0, w2, bn2, wf, stride, prec, *, no_shortcut=None, odd_shortcut=None, t_hi=None):
+    """One alignment feature block in the op's arithmetic: a stride-1 block with the shortcut folded into conv.2's products, a
+    stride-2 block (and any block with a shortcut fault) with the shortcut stored and added as a residual.  Faults, each a mask over
+    the output: ``no_shortcut`` drops the shortcut there, ``odd_shortcut`` makes a stride-2 shortcut read pixel (2i+1, 2j+1) instead
+    of (2i, 2j) there, ``t_hi`` keeps only the hi half of the intermediate t there (t has the output's shape)."""
+    s = (1, stride, stride)
+    t = emulate(x, w0, geo(s, (0, 1, 1)), bn0, None, 1, prec)
+    if t_hi is not None:
+        t = torch.where(t_hi, split(t, prec)[0], t)
+    if stride == 1 and no_shortcut is None:
+        return _emulate_folded(t, x, w2, bn2, wf, prec)
+    f = emulate(x, wf, geo(s), None, None, 0, prec)
+    if odd_shortcut is not None:
+        f_odd = emulate(x[:, :, :, 1::2, 1::2].contiguous(), wf, geo(), None, None, 0, prec)
+        f = torch.where(odd_shortcut, f_odd, f)
+    if no_shortcut is not None:
+        f = f * ~no_shortcut
+    return emulate(t, w2, G_2D, bn2, f, 1, prec)
+
+
+OF_SHAPES = [(1, 1, 16, 32), (2, 2, 16, 32), (1, 3, 32, 16), (1, 10, 16, 32)]   # (B, N, H, W) of the block's input
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
+@pytest.mark.parametrize("regime", ["plain"] + list(eb.REGIMES))
+@pytest.mark.parametrize("block", eb.OF_BLOCKS, ids=lambda b: "%d_%d_s%d" % b)
+@pytest.mark.parametrize("shape", OF_SHAPES, ids=lambda s: "B%dN%d" % s[:2])
+def test_emulated_of_block_within_composed_bound(shape, block, regime, prec):
+    B, N, H, W = shape
+    cin, cout, stride = block
+    x = eb.regime_input(regime, (B, cin, N, H, W), seed=cin + N)
+    wts = eb.of_params(regime, cin, cout, seed=10 * cout + N + stride)
+    y = emulate_of(x, *wts, stride, prec)
+    for r in (eb.of_ref64(x, *wts, stride), eb.of_ref64(x, *wts, stride, prec)):
+        assert torch.isfinite(y).all() and float(r.ref.abs().max()) < 1e4
+        assert eb.check_elementwise(y, r, prec, "OF block %s" % (block,)) <= 0.5
+    if regime == "impulse":
+        assert (r.D == 0).any() and torch.equal(y[r.D == 0], torch.zeros_like(y[r.D == 0]))
+
+
+# block-level faults at the GPU tests' sizes: one 8 x 16 output column of one slice
+OF_FAULT_SHAPE = (2, 10, 64, 128)   # (B, N, H, W) of the block's input
+
+
+@pytest.fixture(scope="module")
+def of_fault_cases():
+    cases = {}
+    for cin, cout, stride in ((8, 8, 1), (8, 16, 2), (16, 32, 2)):
+        gen = torch.Generator().manual_seed(31 + cin)
+        B, N, H, W = OF_FAULT_SHAPE
+        x = F.relu(torch.rand(B, cin, N, H, W, generator=gen) * 2 - 1)      # a previous block's output: post-ReLU
+        wts = eb.of_params("plain", cin, cout, seed=32 + cout)
+        refs = {prec: eb.of_ref64(x, *wts, stride, prec) for prec in ("bf16x3", "fp16", "bf16")}
+        cases[(cin, cout, stride)] = x, wts, refs, {prec: emulate_of(x, *wts, stride, prec) for prec in refs}
+    return cases
+
+
+def test_of_block_fault_free_baseline(of_fault_cases):
+    for x, wts, refs, good in of_fault_cases.values():
+        for prec, y in good.items():
+            assert eb.check_elementwise(y, refs[prec], prec) <= 0.5
+
+
+@pytest.mark.parametrize("block", [(8, 16, 2), (16, 32, 2)], ids=lambda b: "%d_%d" % b[:2])
+def test_of_block_fault_shortcut_reads_the_odd_pixel(of_fault_cases, block):
+    """of_s2's shortcut samples x at (2i+1, 2j+1) instead of (2i, 2j) in one 8 x 16 output column of one slice."""
+    x, wts, refs, good = of_fault_cases[block]
+    mask = _column(good["bf16x3"].shape, 4, 8, 16)
+    for prec in ("bf16x3", "fp16", "bf16"):
+        bad = emulate_of(x, *wts, block[2], prec, odd_shortcut=mask)
+        _record("of shortcut odd pixel", prec, *_block_fault(bad, good[prec], refs[prec], prec))
+
+
+@pytest.mark.parametrize("block", [(8, 8, 1), (8, 16, 2)], ids=lambda b: "%d_%d" % b[:2])
+def test_of_block_fault_missing_shortcut_in_one_column(of_fault_cases, block):
+    x, wts, refs, good = of_fault_cases[block]
+    mask = _column(good["bf16x3"].shape, 7, 16, 32)
+    for prec in ("bf16x3", "fp16", "bf16"):
+        bad = emulate_of(x, *wts, block[2], prec, no_shortcut=mask)
+        _record("of missing shortcut", prec, *_block_fault(bad, good[prec], refs[prec], prec))
+
+
+@pytest.mark.parametrize("block", [(8, 8, 1), (8, 16, 2)], ids=lambda b: "%d_%d" % b[:2])
+def test_of_block_fault_t_from_hi_halves_in_one_strip(of_fault_cases, block):
+    """The block's intermediate t kept as hi halves (the lo half lost) in one strip of 16 pixels of one slice.  Split-bf16 only."""
+    x, wts, refs, good = of_fault_cases[block]
+    mask = _column(good["bf16x3"].shape, 2, 8, 16, h=1)
+    bad = emulate_of(x, *wts, block[2], "bf16x3", t_hi=mask)
+    _record("of t hi only", "bf16x3", *_block_fault(bad, good["bf16x3"], refs["bf16x3"], "bf16x3"))
+
+
 def test_block_faults_that_the_relative_l2_gate_passes():
     """At least three kinds of the faults above pass the kernel-vs-kernel relative-L2 tolerance of their arithmetic, which the block
     tests relied on; the bound sees every one.  (Runs after them, in the file's order.)"""

@@ -16,13 +16,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dffw.h"
-#include "dffw_conv_roll.h"
+#include "dffw_run.h"
 #include "dffw_srd_roll.h"
 #include "dffw_stem.h"
-#include "dffw_conv_tile.h"
-#include "dffw_internal.h"
-#include "dffw_pack.h"
 
 namespace dffw {
 
@@ -30,15 +26,6 @@ namespace dffw {
 static thread_local std::string g_err;
 static thread_local std::string g_last_kernel;   // dffw_last_conv_kernel()
 static thread_local std::string g_last_op_kernels;   // dffw_last_op_kernels()
-static int fail(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 }  // namespace dffw
 int dffw_fail(int code, const char *fmt, ...) {
     char buf[1024];
@@ -50,12 +37,8 @@ int dffw_fail(int code, const char *fmt, ...) {
     return code;
 }
 void dffw_set_last_op_kernels(const char *names) { dffw::g_last_op_kernels = names ? names : ""; }
+void dffw_set_last_conv_kernel(const char *name) { dffw::g_last_kernel = name; }
 namespace dffw {
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) return fail(DFFW_EHIP, "%s -> %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 // ---- layer table -------------------------------------------------------------------------------
 struct ParamInfo {
@@ -219,1097 +202,17 @@ static const Table &table_for(int net) {
     return net == DFFW_NET_E2E ? e2e : depth;
 }
 
-// ---- workspace arena ---------------------------------------------------------------------------
-// Offsets into the caller's workspace; first-fit with coalescing.  The graph is static for a given
-// (B,N,H,W), so a dry run of the same code computes the exact peak (dffw_workspace_bytes).
-class Arena {
-  public:
-    explicit Arena(int64_t cap = INT64_MAX) { free_.push_back({0, cap}); }
-    int64_t alloc(int64_t bytes) {
-        bytes = (bytes + 255) & ~(int64_t)255;
-        for (size_t i = 0; i < free_.size(); ++i) {
-            if (free_[i].second >= bytes) {
-                const int64_t off = free_[i].first;
-                free_[i].first += bytes;
-                free_[i].second -= bytes;
-                if (free_[i].second == 0) free_.erase(free_.begin() + i);
-                live_[off] = bytes;
-                peak_ = std::max(peak_, off + bytes);
-                return off;
-            }
-        }
-        return -1;
-    }
-    void release(int64_t off) {
-        auto it = live_.find(off);
-        if (it == live_.end()) return;
-        std::pair<int64_t, int64_t> blk{off, it->second};
-        live_.erase(it);
-        auto pos = std::lower_bound(free_.begin(), free_.end(), blk);
-        pos = free_.insert(pos, blk);
-        size_t i = pos - free_.begin();
-        if (i + 1 < free_.size() && free_[i].first + free_[i].second == free_[i + 1].first) {
-            free_[i].second += free_[i + 1].second;
-            free_.erase(free_.begin() + i + 1);
-        }
-        if (i > 0 && free_[i - 1].first + free_[i - 1].second == free_[i].first) {
-            free_[i - 1].second += free_[i].second;
-            free_.erase(free_.begin() + i);
-        }
-    }
-    int64_t peak() const { return peak_; }
-
-  private:
-    int64_t peak_ = 0;
-    std::vector<std::pair<int64_t, int64_t>> free_;
-    std::map<int64_t, int64_t> live_;
-};
-
 }  // namespace dffw
 
 using namespace dffw;
 
-extern "C" char **environ;
-
-// ---- engine ------------------------------------------------------------------------------------
-struct ProfRec {
-    std::string kernel, layer;
-    double flops = 0, bytes = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
-struct dffw_engine {
-    int device = 0, net = 0, prec = 0;
-    std::map<std::string, PackedConv> convs;
-    bool profiling = false;
-    std::vector<ProfRec> recs;
-    uint16_t *zero_page = nullptr;  // 256 zero bytes: what out-of-volume LDS-DMA lanes read
-    // side streams + events for the small-shape regime, where single launches cannot fill the chip and the
-    // independent branches of the graph (pyramid scales, regression heads) run next to the main chain
-    static constexpr int NSIDE = 2, NEV = 16;
-    hipStream_t side[NSIDE] = {nullptr, nullptr};
-    hipEvent_t ev[NEV] = {};
-    int ensure_side() {
-        if (side[0]) return DFFW_OK;
-        for (int i = 0; i < NSIDE; ++i) HIPCHK(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
-        for (int i = 0; i < NEV; ++i) HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-        return DFFW_OK;
-    }
-    int ensure_zero_page() {
-        if (zero_page) return DFFW_OK;
-        HIPCHK(hipMalloc((void **)&zero_page, 256));
-        HIPCHK(hipMemset(zero_page, 0, 256));
-        return DFFW_OK;
-    }
-    void clear_recs() {
-        for (auto &r : recs) {
-            if (r.e0) (void)hipEventDestroy(r.e0);
-            if (r.e1) (void)hipEventDestroy(r.e1);
-        }
-        recs.clear();
-    }
-    ~dffw_engine() {
-        clear_recs();
-        if (zero_page) (void)hipFree(zero_page);
-        for (int i = 0; i < NSIDE; ++i)
-            if (side[i]) (void)hipStreamDestroy(side[i]);
-        for (int i = 0; i < NEV; ++i)
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        for (auto &kv : convs) free_packed(kv.second);
-    }
-};
-
 namespace dffw {
 
-static bool getenv_flag(const char *name) {
-    const char *v = getenv(name);
-    return v && *v && *v != '0';
-}
-
-// The DFFW_* kernel-path switches, read from the environment ONCE per forward (Run's constructor): the
-// graph code below never calls getenv itself, so a forward sees one consistent set and pays for one scan of environ.
-#define DFFW_SWITCHES(X)                                                                                                 \
-    X(NO_CONCURRENT) X(NO_CONF_FORK) X(NO_FUSED_ATTENTION) X(NO_FUSED_EFD) X(NO_FUSED_OF) X(NO_FUSED_POOL) X(NO_FUSED_SRD) \
-    X(NO_FUSED_STEM) X(NO_HEAD_SPLIT) X(NO_ROLL) X(NO_ROLL_S2) X(NO_SPLIT) X(NO_SPLITK)  \
-    X(NO_STEM_PAIR) X(NO_TILE) X(NO_SMALL) X(NO_ROLL_S2_WIDE) X(NO_HEAD_SUMS) X(NO_HEAD_SUMS_FUSED) X(NO_HEAD_WARP) X(NO_OF_FIRST) \
-    X(NO_LEAN_TILE) X(NO_LEAN_ROLL) X(NO_ROLLX) X(NO_ROLLK) X(NO_ROLLT) X(NO_TEAMS) X(NO_SLICE32) X(NO_REGRESS_FUSED) X(NO_STEM_PIPE) X(NO_POOL3) X(NO_NARROW)
-enum SwitchId {
-#define X_ID(n) SW_##n,
-    DFFW_SWITCHES(X_ID)
-#undef X_ID
-    SW_COUNT
-};
-// A DFFW_* variable in the environment that nothing reads (a retired switch, a typo) is reported once per process: a retired switch that is silently ignored turns an
-// A/B script into base against base.
-static void warn_unknown_switches() {
-    static bool done = false;
-    if (done) return;
-    done = true;
-    static const char *const known[] = {
-#define X_NM(n) "DFFW_" #n,
-        DFFW_SWITCHES(X_NM)
-#undef X_NM
-        "DFFW_ROLL_WGS", "DFFW_SRD_WGS", "DFFW_SMALL_MAX_UNITS", "DFFW_ROLL_ZSPLIT", "DFFW_KSPLIT_TARGET", "DFFW_SPLIT_S64", "DFFW_SPLIT_T64", "DFFW_NARROW_MAX",
-        "DFFW_WARM_MAX_WGS", "DFFW_ROLLK_MERGE_BELOW", "DFFW_ROLLT_MIN_UNITS", "DFFW_ROLL_MIN_UNITS", "DFFW_SPLIT_WG", "DFFW_DEBUG_FLAGS", "DFFW_CONCURRENT_MAX_PIXELS",
-        "DFFW_SRD_PIPE", "DFFW_REDIR_SIDE", "DFFW_TEAM_MIN_WGS", "DFFW_TEAM_MAX_WGS", "DFFW_CONCURRENT_MIN_PIXELS", "DFFW_TRACE_LAYER", "DFFW_TRACE_OUT", "DFFW_NO_STEM_PAIR", "DFFW_RCCL_LIB", "DFFW_LIB_PATH", "DFFW_NO_PROBE", "DFFW_PRECISION",
-        "DFFW_BENCH_ONE_DEVICE", "DFFW_BENCH_TIMEOUT_S",
-        // development builds only (make ABL=1 / TRACE=1)
-        "DFFW_SRD_ABL", "DFFW_ROLLX_ABL", "DFFW_ROLLX_NTS", "DFFW_ROLLK_ABL", "DFFW_ROLLK_SKEW"};
-    for (char **e = ::environ; e && *e; ++e) {
-        if (strncmp(*e, "DFFW_", 5) != 0) continue;
-        const char *eq = strchr(*e, '=');
-        const size_t n = eq ? (size_t)(eq - *e) : strlen(*e);
-        bool ok = false;
-        for (const char *k : known) ok = ok || (strlen(k) == n && strncmp(k, *e, n) == 0);
-        if (!ok) fprintf(stderr, "libdffw: environment variable %.*s is not a switch this library reads (retired or misspelt?) -- ignored\n", (int)n, *e);
-    }
-}
-
-struct Switches {
-    bool f[SW_COUNT];
-    int roll_wgs = 0, roll_zsplit = 0, srd_wgs = 0, split_wg = 256, debug_flags = 0, small_max_units = 0, roll_min_units = 192, rollt_min_units = 128, rollk_merge_below = 1 << 30, redir_side = -1, team_min_wgs = 0, team_max_wgs = 320, ksplit_target = 512, warm_max_wgs = 1024, narrow_max = 40, split_t64 = 1025, split_s64 = 1025;
-    bool srd_pipe = false;   // DFFW_SRD_PIPE=1: the 16-channel SRD block on srd_pipe16 (one barrier per step) instead of srd_roll16
-    int64_t concurrent_max_pixels = -1;   // < 0: no limit
-    int64_t concurrent_min_pixels = 400000;   // below: one stream (a 5x224x224 stack, 0.25M: 0.799 -> 0.785 ms on one stream; 10x256x256, 0.66M: 0.915 -> 0.905 on three)
-    const char *trace_layer = nullptr, *trace_out = nullptr;
-    bool on(int id) const { return f[id]; }
-    // the switches the kernel launchers consult, as ConvArgs::dbg bits (so that no launcher calls getenv)
-    int path_bits() const;
-    static Switches read() {
-        Switches s;
-        int i = 0;
-#define X_RD(n) s.f[i++] = getenv_flag("DFFW_" #n);
-        DFFW_SWITCHES(X_RD)
-#undef X_RD
-        auto geti = [](const char *name, int lo, int dflt) {
-            const char *z = getenv(name);
-            return (z && atoi(z) >= lo) ? atoi(z) : dflt;
-        };
-        s.roll_wgs = geti("DFFW_ROLL_WGS", 8, 0);
-        s.srd_wgs = geti("DFFW_SRD_WGS", 8, 0);
-        s.small_max_units = geti("DFFW_SMALL_MAX_UNITS", 0, 0);   // (256 measured 6 % faster on one 5x224x224 stack, level on 10x256x256 -- but a
-                                                                  // batch-1 call then differs from the same stack inside a batch by 1.5e-5: off)
-        s.roll_zsplit = geti("DFFW_ROLL_ZSPLIT", 1, 0);
-        s.ksplit_target = geti("DFFW_KSPLIT_TARGET", 1, 512);
-        s.redir_side = geti("DFFW_REDIR_SIDE", 0, -1);   // redir1 / redir2 on the side streams: 1 always, 0 never, unset: from 2M stack pixels
-        s.team_min_wgs = geti("DFFW_TEAM_MIN_WGS", 0, 0);
-        s.team_max_wgs = geti("DFFW_TEAM_MAX_WGS", 1, 320);
-        s.split_s64 = geti("DFFW_SPLIT_S64", 1, 1025);   // ... and a stride-1 3x3x3 layer with 64 outputs (End_to_End dres16_* at batch 8: 0.093 -> 0.076 ms on two 2-tile workgroups per tile; 257 = round 4)
-        s.split_t64 = geti("DFFW_SPLIT_T64", 1, 1025);   // tile count below which a transposed layer with 64 outputs splits its output channels (257 = round 4)
-        s.narrow_max = geti("DFFW_NARROW_MAX", 1, 40);   // widest grid that may take the 5 x 8 x 8 block when its own block leaves the chip short of workgroups (8 = round 4)
-        // conv_tile launches of at most this many (tile, channel-split) workgroups touch the weight lines of their whole contraction walk first
-        // (TileArgs::warm; 0: never).  Measured r03 on 10x256x256 stacks, ms per forward at 0 / 256 / 1024 / always: batch 2 1.29 / 1.17 / 1.17 /
-        // 1.17, batch 8 2.74 / 2.65 / 2.63 / 2.63, batch 16 4.71 / 4.66 / 4.62 / 4.66, batch 32 8.58 / 8.57 / 8.57 / 8.70
-        s.warm_max_wgs = geti("DFFW_WARM_MAX_WGS", 0, 1024);
-        // conv_rollk layers with 64 outputs on fewer columns than this run their two output halves as ONE launch (grid.y = 2); 1: never.  Round 6, same-run layer
-        // tables at batch 32: the 16 x 16-grid layers (128 columns: one unit per CU) 0.058 -> 0.050-0.054 ms against conv_tile, dres0.0 0.099 -> 0.090, dres0.2 /
-        // dres2.conv2 -1..2 % against two launches
-        s.rollk_merge_below = geti("DFFW_ROLLK_MERGE_BELOW", 0, 1 << 30);
-        s.rollt_min_units = geti("DFFW_ROLLT_MIN_UNITS", 1, 128);   // (column, output half) units the transposed streaming kernel conv_rollt needs in its 8-wave forms, 1.5x that in the 4-wave form (DFFW_ROLL_MIN_UNITS lowers it too)
-        s.roll_min_units = geti("DFFW_ROLL_MIN_UNITS", 1, 192);   // columns a layer needs for its persistent streaming kernel (measured 16 ... 256
-                                                                  // at batch 1 and 4: 192 is 3.6 % faster than 256 on one 5x224x224 stack, level elsewhere; <= 32 slower)
-        s.rollt_min_units = std::min(s.rollt_min_units, s.roll_min_units);
-        { const char *z = getenv("DFFW_SPLIT_WG"); s.split_wg = z ? atoi(z) : 256; }   // measured best of 64/128/256/512 at batch 1, 4, 8
-        { const char *z = getenv("DFFW_DEBUG_FLAGS"); s.debug_flags = z ? atoi(z) : 0; }
-        { const char *z = getenv("DFFW_CONCURRENT_MAX_PIXELS"); s.concurrent_max_pixels = z ? atoll(z) : -1; }
-        { const char *z = getenv("DFFW_CONCURRENT_MIN_PIXELS"); if (z) s.concurrent_min_pixels = atoll(z); }
-        s.srd_pipe = getenv_flag("DFFW_SRD_PIPE");
-        warn_unknown_switches();
-        s.trace_layer = getenv("DFFW_TRACE_LAYER");
-        s.trace_out = getenv("DFFW_TRACE_OUT");
-        return s;
-    }
-};
-
-inline int Switches::path_bits() const {
-    return (f[SW_NO_LEAN_TILE] ? DFFW_ARGS_NO_LEAN_TILE : 0) | (f[SW_NO_LEAN_ROLL] ? DFFW_ARGS_NO_LEAN_ROLL : 0) | (f[SW_NO_ROLLX] ? DFFW_ARGS_NO_ROLLX : 0) |
-           (f[SW_NO_ROLLK] ? DFFW_ARGS_NO_ROLLK : 0) | (f[SW_NO_SLICE32] ? DFFW_ARGS_NO_SLICE32 : 0) | (f[SW_NO_ROLLT] ? DFFW_ARGS_NO_ROLLT : 0);
-}
-
-struct ConvOpt {
-    const Act *in1 = nullptr;
-    const Act *res0 = nullptr, *res1 = nullptr;
-    bool res_bcast = false;  // res0 has one slice per sample and is added to every output slice
-    int relu = 0;
-    Act *out_pre = nullptr;  // receives the pre-residual value (allocated here)
-    float *outf = nullptr;   // fp32 planar output (B,outf_ch,N,H,W) instead of an activation volume
-    int outf_ch = 1;
-    const float *fs32 = nullptr;  // stem: read the fp32 focal stack directly (in0 then only carries the geometry)
-    bool raw = false;   // stem: fs32 is a device-side RawStack descriptor (raw uint8 / 0..255 stack, normalised and padded on the fly)
-    float *sums = nullptr;      // per-slice 1x3x3 conv + ReLU whose result only feeds plane sums: nothing is stored, `sums` receives per output
-                                // row segment of 16 pixels [sum | first pixel | last pixel][Cout] fp32 (conv_tile's row-sums variant;
-                                // Run::sums_conv_ok() says when it exists; out is not allocated)
-    const char *cls = nullptr;  // name of a 1x1x1 C->1 layer to apply to the final value inside the epilogue
-    float *cls_out = nullptr;   // its fp32 score volume
-    bool discard = false;       // the activation output itself is not needed (only cls_out / out_pre)
-};
-
-struct Run {
-    dffw_engine *e;
-    hipStream_t s;
-    Arena arena;
-    bool dry;
-    char *ws;
-    int err = DFFW_OK;
-    const dffw_tap *taps = nullptr;
-    int n_taps = 0;
-
-    // ---- branch concurrency (small shapes only; decided from the shape alone so that the dry run that sizes the
-    // workspace takes the same allocation path).  Inside a forked section buffers are not recycled: a block released
-    // after a launch on one stream must not be handed to a launch on another stream that may run earlier.  Outside
-    // it recycling continues as usual — measured: running the whole batch-1 forward without recycling costs 17 %
-    // (the working set stops fitting the last-level cache). ----
-    hipStream_t main_s;
-    bool concurrent = false;
-    bool forked = false;
-    int ev_next = 0;
-    unsigned side_open = 0;   // side streams forked and not yet joined
-    std::vector<void *> deferred;
-
-    const Switches sw;   // the DFFW_* switches as they were when this forward started
-
-    Run(dffw_engine *e_, hipStream_t s_, bool dry_, char *ws_, int64_t cap)
-        : e(e_), s(s_), arena(cap), dry(dry_), ws(ws_), main_s(s_), sw(Switches::read()) {
-        // DFFW_DEBUG_FLAGS bit 0 ("no footprint fill") is withdrawn: kernels then contract uninitialised LDS and the run ended in an abort of the
-        // whole process (profiles/r04_ablation_conv_tile_phases.txt) -- an error code instead; bits 1 (no MFMA loop) and 2 (no stores) remain
-        if (sw.debug_flags & 1) err = fail(DFFW_EINVAL, "DFFW_DEBUG_FLAGS bit 0 (skip the footprint fill) is not supported; use 2 (no MFMA loop), 4 (no stores) or 6");
-    }
-
-    bool ok() const { return err == DFFW_OK; }
-
-    void enable_concurrency() {
-        concurrent = true;
-        if (!dry && ok() && e->ensure_side() != DFFW_OK) err = DFFW_EHIP;
-    }
-    void fork(int k) {   // side stream k continues from the current point of the main stream
-        if (!concurrent || dry || !ok()) return;
-        hipEvent_t v = e->ev[ev_next++ % dffw_engine::NEV];
-        check(hipEventRecord(v, main_s), "fork record");
-        check(hipStreamWaitEvent(e->side[k], v, 0), "fork wait");
-        fork_mark(k);
-    }
-    void on(int k) { s = (concurrent && !dry && k >= 0) ? e->side[k] : main_s; }   // stream of the following launches
-    void fork_mark(int k) { side_open |= 1u << k; }
-    void join(int k) {   // the main stream waits for everything queued on side stream k
-        if (!concurrent || dry || !e->side[k]) return;
-        // (also after an error: kernels already queued on the side stream use the workspace, and the caller is free to
-        // recycle it as soon as the main stream is done)
-        hipEvent_t v = e->ev[ev_next++ % dffw_engine::NEV];
-        const hipError_t h1 = hipEventRecord(v, e->side[k]);
-        const hipError_t h2 = h1 == hipSuccess ? hipStreamWaitEvent(main_s, v, 0) : h1;
-        side_open &= ~(1u << k);
-        if (ok()) check(h2, "join");
-    }
-    ~Run() {   // a forked section left through an error path: join whatever is still open
-        for (int k = 0; k < dffw_engine::NSIDE; ++k)
-            if (side_open & (1u << k)) join(k);
-    }
-    void release_deferred() {
-        for (void *p : deferred) arena.release(dry ? (int64_t)(uintptr_t)p - 256 : (int64_t)((char *)p - ws));
-        deferred.clear();
-    }
-
-    void *raw(int64_t bytes) {
-        if (!ok()) return nullptr;
-        const int64_t off = arena.alloc(bytes);
-        if (off < 0) {
-            err = fail(DFFW_ENOMEM, "workspace too small (need more than the %lld bytes given)", (long long)bytes);
-            return nullptr;
-        }
-        return dry ? (void *)(uintptr_t)(off + 256) : (void *)(ws + off);
-    }
-    void drop_raw(void *p) {
-        if (!p) return;
-        if (forked) {
-            deferred.push_back(p);
-            return;
-        }
-        arena.release(dry ? (int64_t)(uintptr_t)p - 256 : (int64_t)((char *)p - ws));
-    }
-    Act act(int B, int N, int H, int W, int C) {
-        Act a;
-        a.B = B; a.N = N; a.H = H; a.W = W; a.C = C;
-        a.p = (uint16_t *)raw(a.pixels() * prec_parts(e->prec) * C * (int64_t)sizeof(uint16_t));
-        return a;
-    }
-    void drop(Act &a) {
-        drop_raw(a.p);
-        a.p = nullptr;
-    }
-    void check(hipError_t h, const char *what) {
-        if (ok() && h != hipSuccess) err = fail(DFFW_EHIP, "%s: %s", what, hipGetErrorString(h));
-    }
-    // bracket one launch with HIP events on the launch stream (profiling mode only)
-    void prof_begin(const char *kernel, const std::string &layer, double flops, double bytes) {
-        if (!e->profiling || dry || !ok()) return;
-        ProfRec pr;
-        pr.kernel = kernel;
-        pr.layer = layer;
-        pr.flops = flops;
-        pr.bytes = bytes;
-        check(hipEventCreate(&pr.e0), "hipEventCreate");
-        check(hipEventCreate(&pr.e1), "hipEventCreate");
-        if (ok()) check(hipEventRecord(pr.e0, s), "hipEventRecord");
-        e->recs.push_back(pr);
-    }
-    void prof_end() {
-        if (!e->profiling || dry || !ok() || e->recs.empty()) return;
-        check(hipEventRecord(e->recs.back().e1, s), "hipEventRecord");
-    }
-    double elem_bytes() const { return 2.0 * prec_parts(e->prec); }
-
-    // step timeline of a persistent streaming kernel (library built with `make TRACE=1`; DFFW_TRACE_LAYER=<layer> DFFW_TRACE_OUT=<file>):
-    // [workgroup][wave][32 steps][8] u64 of s_memtime stamps (StepTrace, dffw_device.h; tools/trace_steps.py)
-    unsigned long long *trace_dev = nullptr;
-    size_t trace_n = 0;
-    unsigned long long *trace_begin(const std::string &layer, int wgs, int waves) {
-        if (dry || !ok() || !sw.trace_layer || !sw.trace_out || layer != sw.trace_layer) return nullptr;
-        trace_n = (size_t)wgs * waves * 32 * 8;
-        check(hipMalloc((void **)&trace_dev, trace_n * 8), "trace alloc");
-        if (ok()) check(hipMemsetAsync(trace_dev, 0, trace_n * 8, s), "trace memset");
-        return ok() ? trace_dev : nullptr;
-    }
-    void trace_end() {
-        if (!trace_dev) return;
-        if (ok()) {
-            std::vector<unsigned long long> host(trace_n);
-            check(hipStreamSynchronize(s), "trace sync");
-            check(hipMemcpy(host.data(), trace_dev, trace_n * 8, hipMemcpyDeviceToHost), "trace copy");
-            if (FILE *f = fopen(sw.trace_out, "wb")) {
-                fwrite(host.data(), 8, host.size(), f);
-                fclose(f);
-            }
-        }
-        (void)hipFree(trace_dev);
-        trace_dev = nullptr;
-    }
-
-    // does the LDS-tiled kernel serve layer `name` for an output grid of gH x gW (same test as in conv())?
-    bool tiled(const std::string &name, int gH, int gW) const {
-        auto it = e->convs.find(name);
-        if (it == e->convs.end()) return false;
-        const TileCfg *c = it->second.tile.cfg;
-        return c && !sw.on(SW_NO_TILE) && gW * 2 >= c->tx && gH * 2 >= c->ty;
-    }
-
-    // conv_tile's row-sums variant serves per-slice layer `name` on a (B,N,H,W) volume: tiled, an instantiation exists, whole row
-    // segments of 16 pixels, and enough tiles that conv() will not split the output channels over the grid
-    bool sums_conv_ok(const std::string &name, int B, int N, int H, int W) const {
-        if (!tiled(name, H, W)) return false;
-        const TileCfg *c = e->convs.find(name)->second.tile.cfg;
-        if (!tile_cfg_has_sums(c) || W % c->tx) return false;
-        const int64_t tiles = (int64_t)B * ((N + c->tz - 1) / c->tz) * ((H + c->ty - 1) / c->ty) * (W / c->tx);
-        return tiles >= 256;
-    }
-
-    Act conv(const std::string &name, const Act &in0, const ConvOpt &o = ConvOpt()) {
-        Act out;
-        if (!ok()) return out;
-        auto it = e->convs.find(name);
-        if (it == e->convs.end()) {
-            err = fail(DFFW_EINVAL, "no packed layer %s", name.c_str());
-            return out;
-        }
-        const PackedConv &pc = it->second;
-        const LayerDef &L = pc.def;
-        const int cin = in0.C + (o.in1 ? o.in1->C : 0);
-        const int cin_pad = pc.cin_all;
-        if (cin != cin_pad) {
-            err = fail(DFFW_EINVAL, "layer %s expects %d input channels, got %d", name.c_str(), cin_pad, cin);
-            return out;
-        }
-        int Ho, Wo;
-        if (L.transposed) {
-            Ho = in0.H * 2;
-            Wo = in0.W * 2;
-        } else {
-            const int win = (L.kh == 9 && L.cin == 3) ? in0.W - 2 : in0.W;  // stem input is the (W+2)-wide paired volume
-            Ho = (in0.H + 2 * L.ph - L.dh * (L.kh - 1) - 1) / L.sh + 1;
-            Wo = (win + 2 * L.pw - L.dw * (L.kw - 1) - 1) / L.sw + 1;
-        }
-        const int No = in0.N + 2 * L.pd - (L.kd - 1);
-        if (o.outf == nullptr && !o.discard && !o.sums) out = act(in0.B, No, Ho, Wo, L.cout);
-        else { out.B = in0.B; out.N = No; out.H = Ho; out.W = Wo; out.C = L.cout; }
-        const float *cls_w = nullptr;
-        if (o.cls) {
-            auto ic = e->convs.find(o.cls);
-            if (ic == e->convs.end() || !ic->second.w32 || ic->second.def.cin != L.cout || ic->second.def.cout != 1) {
-                err = fail(DFFW_EINVAL, "cannot fuse classifier %s into %s", o.cls, name.c_str());
-                return out;
-            }
-            cls_w = ic->second.w32;
-        }
-        if (o.out_pre) *o.out_pre = act(in0.B, No, Ho, Wo, L.cout);
-        if (!ok()) return out;
-        // (the dry run that sizes the workspace continues through the launch planning below: split-K adds a scratch block)
-
-        ConvArgs a;
-        memset(&a, 0, sizeof a);
-        a.in0 = in0.p;
-        a.C0 = in0.C;
-        a.in1 = o.in1 ? o.in1->p : in0.p;
-        a.C1 = o.in1 ? o.in1->C : 0;
-        a.B = in0.B; a.Ni = in0.N; a.Hi = in0.H; a.Wi = in0.W;
-        a.No = No; a.Ho = Ho; a.Wo = Wo;
-        a.Cout = L.cout;
-        a.bias = pc.bias;
-        a.res0 = o.res0 ? o.res0->p : nullptr;
-        a.res1 = o.res1 ? o.res1->p : nullptr;
-        a.res_bcast = o.res_bcast ? 1 : 0;
-        if (o.res_bcast && !(L.kd == 1 && L.kh == 3 && !L.transposed && L.sh == 1 && L.cout >= 16)) {
-            err = fail(DFFW_EINVAL, "slice-broadcast residual is only implemented for the per-slice 1x3x3 convs (layer %s)", name.c_str());
-            return out;
-        }
-        a.out = out.p;
-        a.out_pre = o.out_pre ? o.out_pre->p : nullptr;
-        a.outf = o.outf;
-        a.fs32 = o.fs32;
-        a.outf_ch = o.outf_ch;
-        a.outf_plane = (int64_t)No * Ho * Wo;
-        a.cls_w = cls_w;
-        a.cls_out = o.cls_out;
-        a.relu = o.relu;
-        if (!dry && e->ensure_zero_page() != DFFW_OK) { err = DFFW_EHIP; return out; }
-        a.zero = e->zero_page;
-        a.dbg = (sw.debug_flags & 6) | sw.path_bits();   // ablation switches (2 no MFMA loop, 4 no stores) + the launchers' path switches
-        if (o.raw) a.dbg |= DFFW_ARGS_RAW;   // fs32 then points to the RawStack descriptor in device memory
-        if (o.sums) {
-            if (!sums_conv_ok(name, in0.B, in0.N, in0.H, in0.W) || o.relu != 1 || o.res0 || o.res1 || o.cls || o.out_pre || o.in1) {
-                err = fail(DFFW_EINVAL, "layer %s has no row-sums kernel for this shape / epilogue", name.c_str());
-                return out;
-            }
-            a.outf = o.sums;
-            a.dbg |= DFFW_ARGS_SUMS;
-        }
-        // transposed 32 / 64 -> 32 / 64 (deconv_1, dres2.conv5 / conv6, dres3.conv5, SPP conv9) on 8 x 8 columns of the input grid: the streaming kernel with the
-        // filter split over the waves by output phase; a unit = (column, 32-channel output half)
-        if (pc.wrollt && !o.in1 && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_ROLLT)) {
-            int tty, ttx;
-            rollt_tile(L.cout, &tty, &ttx);
-            const int cols = ((in0.H + tty - 1) / tty) * ((in0.W + ttx - 1) / ttx);   // (partial columns are predicated in the kernel)
-            ConvArgs ak = a;
-            ak.Ng = in0.N; ak.Hg = in0.H; ak.Wg = in0.W;
-            ak.M = (int64_t)ak.B * in0.N * in0.H * in0.W;
-            // (column, output half) units from which the kernel beats conv_tile / conv_roll_t32, measured at batch 8 / 16 / 32 (profiles/r06_rollt_thresholds.txt): 128 for the
-            // 8-wave forms -- half the CUs busy, and still 0.046 vs 0.058 ms on deconv_1 at batch 8, 0.052 vs 0.072 on SPP conv9 at batch 32; 64 units lose --, 192 for the 4-wave form
-            const int64_t rt_units = (int64_t)in0.B * cols * std::max(1, L.cout / 32);
-            const bool rt_four = cin_pad == 32 && L.cout != 16;
-            if (rt_units >= (int64_t)sw.rollt_min_units * (rt_four ? 3 : 2) / 2 && rollt_ok(e->prec, ak)) {
-                if (dry) return out;
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wrollt;
-                t.tiles_y = (in0.H + tty - 1) / tty;
-                t.tiles_x = (in0.W + ttx - 1) / ttx;
-                t.zsplit = 1;
-                t.total_tiles = in0.B * cols;
-                t.wgs = sw.roll_wgs;
-                char kn[96];
-                conv_rollt_kernel_name(ak, kn, sizeof kn);
-                g_last_kernel = kn;
-                const double opx = (double)out.B * No * Ho * Wo;
-                // the fused classifier's two partial dots per pixel are ADDED to the score volume
-                if (ak.cls_w) check(hipMemsetAsync(ak.cls_out, 0, (size_t)(opx * 4.0), s), "score memset");
-                if (e->profiling) {
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes()
-                                         + opx * L.cout * elem_bytes() * ((o.discard ? 0 : 1) + (o.out_pre ? 1 : 0) + (o.res0 ? 1 : 0)) + (o.cls ? opx * 4.0 : 0.0)
-                                         + 27.0 * L.cin * L.cout * elem_bytes();
-                    prof_begin(kn, name, 2.0 * (double)ak.M * 27.0 * L.cin * L.cout, bytes);
-                }
-                check(launch_conv_rollt(ak, t, s), name.c_str());
-                prof_end();
-                return out;
-            }
-        }
-        // transposed 32 -> 16 (deconv_2, dres3.conv6): two sweeps of conv_roll_t32, one per output row phase
-        if (pc.wroll_t32 && (in0.C == 32 || in0.C == 16) && !o.in1 && !o.res_bcast && !o.res1 && !o.outf && in0.H % 8 == 0 && in0.W % 16 == 0 &&
-            (int64_t)in0.B * (in0.H / 8) * (in0.W / 16) >= sw.roll_min_units && !sw.on(SW_NO_ROLL)) {
-            if (dry) return out;
-            a.Ng = in0.N; a.Hg = in0.H; a.Wg = in0.W;
-            a.M = (int64_t)a.B * in0.N * in0.H * in0.W;
-            a.dbg &= (6 | DFFW_ARGS_NO_LEAN_TILE | DFFW_ARGS_NO_LEAN_ROLL | DFFW_ARGS_NO_ROLLX | DFFW_ARGS_NO_ROLLK | DFFW_ARGS_NO_SLICE32);   // (the ablation bits these kernels know + the launchers' path switches)
-            for (int py = 0; py < 2; ++py) {
-                int rty, rtx;
-                roll_t32_tile(py, &rty, &rtx);
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                const int parts = prec_parts(e->prec);
-                t.wroll = pc.wroll_t32 + (size_t)(py ? ROLL_CHUNKS_T32_0 : 0) * parts * 512;
-                t.tiles_y = in0.H / rty;
-                t.tiles_x = in0.W / rtx;
-                t.zsplit = 1;
-                t.total_tiles = in0.B * t.tiles_y * t.tiles_x;
-                t.wgs = sw.roll_wgs;
-                char kn[96];
-                conv_roll_t32_kernel_name(e->prec, py, a, kn, sizeof kn);
-                g_last_kernel = kn;
-                if (e->profiling) {
-                    const double opx = (double)out.B * No * Ho * Wo * 0.5;   // this sweep's output pixels
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes()
-                                         + opx * L.cout * elem_bytes() * ((o.discard ? 0 : 1) + (o.out_pre ? 1 : 0) + (o.res0 ? 1 : 0)) + (o.cls ? opx * 4.0 : 0.0);
-                    prof_begin(kn, name + (py ? " (odd rows)" : " (even rows)"), 2.0 * (double)a.M * (py ? 18.0 : 9.0) * L.cin * L.cout, bytes);
-                }
-                check(launch_conv_roll_t32(e->prec, py, a, t, s), name.c_str());
-                prof_end();
-            }
-            return out;
-        }
-        // strided 3x3x3 over 16 / 32 channels (FM_conv2.0.stride_conv, dres3.conv1, dres4.conv3; dres3.conv3, dres2.conv1, SPP conv1):
-        // rolling window with whole pixel records
-        if (pc.wroll_s2 && !L.transposed && L.sh == 2 && (in0.C == 16 || in0.C == 32) && !o.in1 && !o.res1 && !o.res_bcast && !o.outf && !o.out_pre &&
-            !o.cls && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_ROLL_S2) &&
-            (L.cout <= 32 || !sw.on(SW_NO_ROLL_S2_WIDE))) {   // 32 -> 64 as two launches: level with conv_tile in r02, 4-7 % faster since the r04 row-pitch fix of conv_roll_s2
-            const int khn = in0.C / 16;
-            const int ntk = (khn == 2 || L.cout >= 32) ? 2 : 1;     // output tiles per launch
-            const int nlaunch = (L.cout / 16 + ntk - 1) / ntk;
-            int sty, stx;
-            s2_roll_tile(ntk, &sty, &stx);
-            if ((L.cout / 16) % ntk == 0 && Ho % sty == 0 && Wo % stx == 0 && in0.H == 2 * Ho && in0.W == 2 * Wo &&
-                (int64_t)in0.B * (Ho / sty) * (Wo / stx) >= sw.roll_min_units) {
-                if (dry) return out;
-                a.Ng = No; a.Hg = Ho; a.Wg = Wo;
-                a.M = (int64_t)a.B * No * Ho * Wo;
-                a.dbg &= (6 | DFFW_ARGS_NO_LEAN_TILE | DFFW_ARGS_NO_LEAN_ROLL | DFFW_ARGS_NO_ROLLX | DFFW_ARGS_NO_ROLLK | DFFW_ARGS_NO_SLICE32);   // (the ablation bits these kernels know + the launchers' path switches)
-                for (int li = 0; li < nlaunch; ++li) {
-                    RollArgs t;
-                    memset(&t, 0, sizeof t);
-                    t.wroll = pc.wroll_s2;
-                    t.tiles_y = Ho / sty;
-                    t.tiles_x = Wo / stx;
-                    t.zsplit = 1;
-                    t.total_tiles = in0.B * t.tiles_y * t.tiles_x;
-                    t.wgs = sw.roll_wgs;
-                    t.pair = li * ntk;     // first 16-channel output tile of this launch
-                    char kn[96];
-                    conv_roll_s2_kernel_name(e->prec, ntk, khn, a, kn, sizeof kn);
-                    g_last_kernel = kn;
-                    if (e->profiling) {
-                        const double opx = (double)out.B * No * Ho * Wo;
-                        prof_begin(kn, nlaunch > 1 ? name + (li ? " (upper output channels)" : " (lower output channels)") : name,
-                                   2.0 * opx * 27.0 * L.cin * L.cout / nlaunch,
-                                   ((double)in0.pixels() * L.cin + opx * L.cout / nlaunch * (1 + (o.res0 ? 1 : 0))) * elem_bytes() + 27.0 * L.cin * L.cout / nlaunch * elem_bytes());
-                    }
-                    check(launch_conv_roll_s2(e->prec, ntk, khn, a, t, s), name.c_str());
-                    prof_end();
-                }
-                return out;
-            }
-        }
-        // strided 3x3x3 8 -> 16 (dres4.conv1): the single-branch form of conv_roll_efd
-        {
-            int ety, etx;
-            efd_roll_tile(&ety, &etx);
-            if (pc.wroll8 && !L.transposed && L.sh == 2 && in0.C == 8 && !o.in1 && !o.res0 && !o.res1 && !o.res_bcast && !o.outf && !o.out_pre &&
-                !o.cls && Ho % ety == 0 && Wo % etx == 0 && (int64_t)in0.B * (Ho / ety) * (Wo / etx) >= sw.roll_min_units && !sw.on(SW_NO_ROLL) &&
-                !sw.on(SW_NO_ROLL_S2)) {
-                if (dry) return out;
-                a.Ng = No; a.Hg = Ho; a.Wg = Wo;
-                a.M = (int64_t)a.B * No * Ho * Wo;
-                a.dbg &= (6 | DFFW_ARGS_NO_LEAN_TILE | DFFW_ARGS_NO_LEAN_ROLL | DFFW_ARGS_NO_ROLLX | DFFW_ARGS_NO_ROLLK | DFFW_ARGS_NO_SLICE32);   // (the ablation bits these kernels know + the launchers' path switches)
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wroll8;
-                t.tiles_y = Ho / ety;
-                t.tiles_x = Wo / etx;
-                t.zsplit = 1;
-                t.total_tiles = in0.B * t.tiles_y * t.tiles_x;
-                t.wgs = sw.roll_wgs;
-                char kn[96];
-                conv_roll_efd_kernel_name(e->prec, a, false, kn, sizeof kn);
-                g_last_kernel = kn;
-                if (e->profiling) {
-                    const double opx = (double)out.B * No * Ho * Wo;
-                    prof_begin(kn, name, 2.0 * opx * 27.0 * L.cin * L.cout,
-                               ((double)in0.pixels() * L.cin + opx * L.cout) * elem_bytes() + 27.0 * L.cin * L.cout * elem_bytes());
-                }
-                check(launch_conv_roll_efd(e->prec, a, t, s), name.c_str());
-                prof_end();
-                return out;
-            }
-        }
-        // ... and its transposed sibling (16 -> 8 channels), tiled over the input grid
-        {
-            int rty, rtx;
-            roll_tile(&rty, &rtx);
-            const int cols = (in0.H / rty) * (in0.W / rtx);
-            if (pc.wroll_t && in0.H % rty == 0 && in0.W % rtx == 0 && in0.C == 16 && !o.in1 && !o.res_bcast && !o.res1 && !o.outf &&
-                (int64_t)in0.B * cols >= sw.roll_min_units && !sw.on(SW_NO_ROLL)) {
-                if (dry) return out;
-                a.Ng = in0.N; a.Hg = in0.H; a.Wg = in0.W;
-                a.M = (int64_t)a.B * in0.N * in0.H * in0.W;
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wroll_t;
-                t.tiles_y = in0.H / rty;
-                t.tiles_x = in0.W / rtx;
-                t.zsplit = ((int64_t)in0.B * cols < 1024 && No >= 8) ? 2 : 1;
-                if (sw.roll_zsplit >= 1 && sw.roll_zsplit <= No) t.zsplit = sw.roll_zsplit;
-                t.total_tiles = in0.B * t.zsplit * cols;
-                t.wgs = 0;
-                if (sw.roll_wgs) t.wgs = sw.roll_wgs;
-                t.pair = 1;
-                char kn[96];
-                conv_roll_t_kernel_name(e->prec, a, kn, sizeof kn);
-                g_last_kernel = kn;
-                if (e->profiling) {
-                    const double opx = (double)out.B * No * Ho * Wo;
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes()
-                                         + opx * L.cout * elem_bytes() * ((o.discard ? 0 : 1) + (o.out_pre ? 1 : 0))
-                                         + opx * L.cout * elem_bytes() * (o.res0 ? 1 : 0) + (o.cls ? opx * 4.0 : 0.0)
-                                         + 27.0 * L.cin * L.cout * elem_bytes();
-                    prof_begin(kn, name, 2.0 * (double)a.M * 27.0 * L.cin * L.cout, bytes);
-                }
-                check(launch_conv_roll_t(e->prec, a, t, s), name.c_str());
-                prof_end();
-                return out;
-            }
-        }
-        // the stem straight from the focal stack: pixel-pair form (half the MFMAs and LDS reads of the per-pixel kernel)
-        const bool stem_pair = o.fs32 && pc.tile_pair.cfg && pc.bias_pair && Wo % pc.tile_pair.cfg->tx == 0 && Ho % pc.tile_pair.cfg->ty == 0 &&
-                               !sw.on(SW_NO_STEM_PAIR);
-        if (stem_pair) a.bias = pc.bias_pair;
-        const int gW = L.transposed ? in0.W : Wo, gH = L.transposed ? in0.H : Ho;
-        // the 5 x 8 x 8 block (its packs of layers with more than 4 output tiles split the output channels over grid.y: not with a fused classifier,
-        // whose partial dot spans all of a pixel's channels, nor under DFFW_NO_SPLIT), with enough samples / tiles to fill the chip:
-        // (a) grids at most 8 x 8 (the 1/32-resolution pyramid layers at 256 x 256, round 4);  (b) round 5: stride-1 layers with 128 output channels on grids up to
-        // DFFW_NARROW_MAX (40) wide -- End_to_End's 30 x 40 pyramid level at batch 8: `combine2` / `conv4` ran on the 4 x 4 x 8 block with all 128 output
-        // channels per workgroup, re-streaming the filter for 128 grid points at a time (0.24 -> 0.13 ms, `conv4` 0.16 -> 0.09; the 64-output layers of those levels gain 2-8 % on it at that shape and lose as much at others: left alone)
-        const bool narrow_splits = pc.tile_narrow.cfg && pc.nt > pc.tile_narrow.cfg->nt;
-        const int gN = L.transposed ? in0.N : No;
-        bool narrow = !stem_pair && pc.tile_narrow.cfg && !sw.on(SW_NO_NARROW) && !(narrow_splits && (o.cls || sw.on(SW_NO_SPLIT))) &&
-                      (int64_t)in0.B * ((gN + 4) / 5) * ((gH + 7) / 8) * ((gW + 7) / 8) * pc.nt >= 256;
-        if (narrow && !(gW <= 8 && gH <= 8)) narrow = !L.transposed && pc.nt >= 8 && gW <= sw.narrow_max && gH <= sw.narrow_max;
-        const TilePack &tp = stem_pair ? pc.tile_pair : (narrow ? pc.tile_narrow : pc.tile);
-        // 32 -> 16 channels on whole 8 x 16 columns: the pipelined rolling window with the contraction split over the two input halves
-        {
-            const int cols = (Ho / 8) * (Wo / 16);
-            const bool halves = o.in1 ? (in0.C == 16 && o.in1->C == 16) : in0.C == 32;
-            if (pc.wroll_k2 && halves && Ho % 8 == 0 && Wo % 16 == 0 && (int64_t)in0.B * cols >= sw.roll_min_units && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_ROLLX)) {
-                ConvArgs ak = a;
-                ak.Ng = No; ak.Hg = Ho; ak.Wg = Wo;
-                ak.M = (int64_t)ak.B * No * Ho * Wo;
-                if (rollx_k2_ok(e->prec, ak)) {
-                    if (dry) return out;
-                    RollArgs t;
-                    memset(&t, 0, sizeof t);
-                    t.wroll = pc.wroll_k2;
-                    t.tiles_y = Ho / 8;
-                    t.tiles_x = Wo / 16;
-                    t.zsplit = ((int64_t)in0.B * cols < 512 && No >= 8) ? 2 : 1;
-                    if (sw.roll_zsplit >= 1 && sw.roll_zsplit <= No) t.zsplit = sw.roll_zsplit;
-                    t.total_tiles = in0.B * t.zsplit * cols;
-                    t.wgs = sw.roll_wgs;
-                    char kn[96];
-                    conv_rollx_k2_kernel_name(ak, kn, sizeof kn);
-                    g_last_kernel = kn;
-                    if (e->profiling) {
-                        const double opx = (double)out.B * No * Ho * Wo;
-                        const double bytes = (double)in0.pixels() * L.cin * elem_bytes() + opx * L.cout * elem_bytes() + 27.0 * L.cin * L.cout * elem_bytes();
-                        prof_begin(kn, name, 2.0 * opx * 27.0 * L.cin * L.cout, bytes);
-                    }
-                    check(launch_conv_rollx_k2(ak, t, s), name.c_str());
-                    prof_end();
-                    return out;
-                }
-            }
-        }
-        // per-slice 1x3x3, 32 -> 32 channels on whole 8 x 16 columns: the streaming kernel with the filter resident in every wave
-        if (pc.wslice32 && !o.in1 && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_SLICE32)) {
-            int sty, stx;
-            slice32_tile(&sty, &stx);
-            const int cols = (Ho / sty) * (Wo / stx);
-            ConvArgs ak = a;
-            ak.Ng = No; ak.Hg = Ho; ak.Wg = Wo;
-            ak.M = (int64_t)ak.B * No * Ho * Wo;
-            if (Ho % sty == 0 && Wo % stx == 0 && (int64_t)in0.B * cols >= sw.roll_min_units && slice32_ok(e->prec, ak)) {
-                if (dry) return out;
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wslice32;
-                t.tiles_y = Ho / sty;
-                t.tiles_x = Wo / stx;
-                t.zsplit = 1;
-                t.total_tiles = in0.B * cols;
-                t.wgs = sw.roll_wgs;
-                char kn[96];
-                conv_slice32_kernel_name(ak, kn, sizeof kn);
-                g_last_kernel = kn;
-                if (e->profiling) {
-                    const double opx = (double)out.B * No * Ho * Wo;
-                    const double obytes = o.sums ? opx / 16.0 * 3.0 * L.cout * 4.0 : opx * L.cout * elem_bytes() * (1 + (o.res0 ? 1 : 0));
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes() + obytes + 9.0 * L.cin * L.cout * elem_bytes();
-                    prof_begin(kn, name, 2.0 * opx * 9.0 * L.cin * L.cout, bytes);
-                }
-                check(launch_conv_slice32(ak, t, s), name.c_str());
-                prof_end();
-                return out;
-            }
-        }
-        // per-slice 1x3x3, 64 -> 64 channels on whole 8 x 16 columns: the streaming kernel with one output tile's filter resident per wave
-        if (pc.wslice64 && (pc.slice_cat ? (o.in1 && o.in1->C == 32) : !o.in1) && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_SLICE32)) {
-            int sty, stx;
-            slice32_tile(&sty, &stx);
-            const int cols = (Ho / sty) * (Wo / stx);
-            ConvArgs ak = a;
-            ak.Ng = No; ak.Hg = Ho; ak.Wg = Wo;
-            ak.M = (int64_t)ak.B * No * Ho * Wo;
-            if (Ho % sty == 0 && Wo % stx == 0 && (int64_t)in0.B * cols >= sw.roll_min_units && slice64_ok(e->prec, ak)) {
-                if (dry) return out;
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wslice64;
-                t.tiles_y = Ho / sty;
-                t.tiles_x = Wo / stx;
-                t.zsplit = 1;
-                t.total_tiles = in0.B * cols;
-                t.wgs = sw.roll_wgs;
-                char kn[96];
-                conv_slice64_kernel_name(ak, kn, sizeof kn);
-                g_last_kernel = kn;
-                if (e->profiling) {
-                    const double opx = (double)out.B * No * Ho * Wo;
-                    const double obytes = o.sums ? opx / 16.0 * 3.0 * L.cout * 4.0 : opx * L.cout * elem_bytes();
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes() + obytes + 9.0 * L.cin * L.cout * elem_bytes();
-                    prof_begin(kn, name, 2.0 * opx * 9.0 * L.cin * L.cout, bytes);
-                }
-                check(launch_conv_slice64(ak, t, s), name.c_str());
-                prof_end();
-                return out;
-            }
-        }
-        // 32 / 64 -> 32 / 64 channels on whole 8 x 8 columns: the K-split rolling window (one launch per 32 output channels)
-        if (pc.wrollk && !sw.on(SW_NO_ROLL) && !sw.on(SW_NO_ROLLK)) {
-            int kty, ktx;
-            rollk_tile(&kty, &ktx);
-            const int cols = ((Ho + kty - 1) / kty) * ((Wo + ktx - 1) / ktx);   // (partial columns at the bottom / right edge are predicated in the kernel)
-            ConvArgs ak = a;
-            ak.Ng = No; ak.Hg = Ho; ak.Wg = Wo;
-            ak.M = (int64_t)ak.B * No * Ho * Wo;
-            // 64 output channels = two 32-channel halves as grid.y of ONE launch (round 6: the 16 x 16-grid layers `dres16_*`, `conv2`, `dres2.conv4` at batch 32
-            // are 128 columns x 2 halves = one unit per CU and now take this kernel; DFFW_ROLLK_MERGE_BELOW=1: two launches)
-            const int npair = L.cout / 32;
-            const bool merged = npair == 2 && (int64_t)in0.B * cols < sw.rollk_merge_below;
-            if ((int64_t)in0.B * cols * (merged ? npair : 1) >= sw.roll_min_units && rollk_waves(e->prec, ak) == cin_pad / 8) {
-                if (dry) return out;
-                const int nlaunch = merged ? 1 : npair;
-                for (int op = 0; op < nlaunch; ++op) {
-                    RollArgs t;
-                    memset(&t, 0, sizeof t);
-                    t.wroll = pc.wrollk + (size_t)op * (cin_pad / 8) * ROLLK_CHUNKS * 2 * prec_parts(e->prec) * 512;
-                    t.tiles_y = (Ho + kty - 1) / kty;
-                    t.tiles_x = (Wo + ktx - 1) / ktx;
-                    // a sample's slices as two ranges where whole columns leave the chip short of workgroups (16 waves per CU: 256 8-wave / 512 4-wave units)
-                    t.zsplit = ((int64_t)in0.B * cols * (merged ? npair : 1) < (cin_pad == 64 && merged ? 256 : 512) && No >= 8) ? 2 : 1;
-                    if (sw.roll_zsplit >= 1 && sw.roll_zsplit <= No) t.zsplit = sw.roll_zsplit;
-                    t.total_tiles = in0.B * t.zsplit * cols;
-                    t.wgs = sw.roll_wgs;
-                    t.pair = merged ? -1 : op * 2;     // first 16-channel output tile of this launch (-1: every half, as grid.y)
-                    char kn[96];
-                    conv_rollk_kernel_name(ak, kn, sizeof kn);
-                    g_last_kernel = kn;
-                    if (e->profiling) {
-                        const double opx = (double)out.B * No * Ho * Wo;
-                        const double bytes = (double)in0.pixels() * L.cin * elem_bytes() + opx * L.cout / nlaunch * elem_bytes() * (1 + (o.res0 ? 1 : 0)) +
-                                             27.0 * L.cin * L.cout / nlaunch * elem_bytes();
-                        prof_begin(kn, nlaunch > 1 ? name + (op ? " (upper output channels)" : " (lower output channels)") : name,
-                                   2.0 * opx * 27.0 * L.cin * L.cout / nlaunch, bytes);
-                    }
-                    check(launch_conv_rollk(ak, t, s), name.c_str());
-                    prof_end();
-                }
-                return out;
-            }
-        }
-        // rolling-window kernel: 16-channel 3x3x3 stride-1 layers whose grid is whole columns and fills the chip
-        {
-            int rty, rtx;
-            roll_tile(&rty, &rtx);
-            const int cols = (Ho / rty) * (Wo / rtx);
-            if (pc.wroll && Ho % rty == 0 && Wo % rtx == 0 && in0.C % 8 == 0 && (!o.in1 || o.in1->C == in0.C) && !o.res_bcast && !o.res1 &&
-                (int64_t)in0.B * cols >= sw.roll_min_units && !sw.on(SW_NO_ROLL)) {
-                if (dry) return out;
-                a.Ng = No; a.Hg = Ho; a.Wg = Wo;
-                a.M = (int64_t)a.B * No * Ho * Wo;
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = pc.wroll;
-                t.tiles_y = Ho / rty;
-                t.tiles_x = Wo / rtx;
-                t.zsplit = ((int64_t)in0.B * cols < 1024 && No >= 8) ? 2 : 1;
-                if (sw.roll_zsplit >= 1 && sw.roll_zsplit <= No) t.zsplit = sw.roll_zsplit;
-                t.total_tiles = in0.B * t.zsplit * cols;
-                t.wgs = 0;
-                t.pair = pc.roll_pair ? 1 : 0;
-                if (sw.roll_wgs) t.wgs = sw.roll_wgs;
-                {
-                    char kn[96];
-                    conv_roll_kernel_name(e->prec, a, pc.roll_pair, kn, sizeof kn);
-                    g_last_kernel = kn;
-                }
-                if (e->profiling) {
-                    char kn[96];
-                    conv_roll_kernel_name(e->prec, a, pc.roll_pair, kn, sizeof kn);
-                    const double opx = (double)out.B * No * Ho * Wo;
-                    const double bytes = (double)in0.pixels() * L.cin * elem_bytes()
-                                         + opx * L.cout * (o.outf ? 4.0 : elem_bytes() * (o.out_pre ? 2 : 1))
-                                         + opx * L.cout * elem_bytes() * ((o.res0 ? 1 : 0) + (o.res1 ? 1 : 0))
-                                         + 27.0 * L.cin * L.cout * elem_bytes();
-                    prof_begin(kn, name, 2.0 * opx * 27.0 * L.cin * L.cout, bytes);
-                }
-                a.trace = trace_begin(name, 1024, 4);
-                check(launch_conv_roll(e->prec, a, t, s), name.c_str());
-                prof_end();
-                trace_end();
-                return out;
-            }
-        }
-        // small grids (the low-resolution pyramid at batch 1): conv_small's one-workgroup-per-(16 points, 16 channels) split of the
-        // whole layer beats an LDS tile that a few workgroups walk stage by stage (+ a split-K finish launch)
-        const int64_t small_units = ((int64_t)in0.B * (L.transposed ? in0.N : No) * gH * gW + 15) / 16 * pc.nt;
-        const bool prefer_small = small_units <= sw.small_max_units && !o.cls && !o.fs32 && !sw.on(SW_NO_SMALL) && !stem_pair;
-        const bool use_tile = tp.cfg && !sw.on(SW_NO_TILE) && gW * 2 >= tp.cfg->tx && gH * 2 >= tp.cfg->ty &&
-                              in0.C % 8 == 0 && (!o.in1 || o.in1->C % 8 == 0) && !prefer_small;
-        if (use_tile) {
-            const TileCfg *cfg = tp.cfg;   // may be replaced by a narrower instantiation of the same tile (channel split)
-            a.Ng = L.transposed ? in0.N : No;
-            a.Hg = gH;
-            a.Wg = gW;
-            a.sy = a.sx = L.transposed ? 1 : L.sh;
-            a.osy = a.osx = L.transposed ? 2 : 1;
-            a.M = (int64_t)a.B * a.Ng * a.Hg * a.Wg;
-            TileArgs t;
-            memset(&t, 0, sizeof t);
-            t.npass = tp.npass;
-            t.nstage = tp.nstage;
-            double flops = 0;
-            for (int ps = 0; ps < tp.npass; ++ps) {
-                t.KC[ps] = tp.KC[ps];
-                t.tab[ps] = tp.tab[ps];
-                t.wpk[ps] = tp.wpk[ps];
-                t.ooy[ps] = tp.ooy[ps];
-                t.oox[ps] = tp.oox[ps];
-                flops += 2.0 * (double)a.M * (L.transposed ? tp.ntaps[ps] : L.kd * L.kh * L.kw) * L.cin * L.cout;
-            }
-            t.tiles_z = (a.Ng + cfg->tz - 1) / cfg->tz;
-            t.tiles_y = (a.Hg + cfg->ty - 1) / cfg->ty;
-            t.tiles_x = (a.Wg + cfg->tx - 1) / cfg->tx;
-            t.total_tiles = a.B * t.tiles_z * t.tiles_y * t.tiles_x;
-            t.nt_total = pc.nt;
-            t.nsplit = pc.nt / cfg->nt;   // (1, except the narrow packs of layers with more than 4 output tiles)
-            // few-tile layers (the 1/16..1/32-resolution pyramid, or batch 1): split the output channels over
-            // grid.y so that at least ~one workgroup per CU exists
-            // (3x3x3 stride-1 and transposed layers also at exactly one tile per CU -- the 16x16-grid layers at batch 32: two 32-channel
-            // workgroups per tile keep three workgroups resident instead of two, -10 % on those layers; the stride-2 layers lose 40 % with it)
-            // (transposed layers with 64 outputs: the 4-output-tile block runs at 127 TFLOP/s where two launches' worth of 2-tile workgroups run at 212 -- measured on End_to_End's
-            // `dres2.conv5`, 384 tiles at batch 8 --, so they split up to 1024 tiles)
-            const int split_below = (cfg->geo == G3T && pc.nt >= 4) ? sw.split_t64 : (cfg->geo == G3S1 && pc.nt == 4) || (cfg->geo == G3S2 && pc.nt >= 8) ? sw.split_s64 : ((cfg->geo == G3S1 || cfg->geo == G3T) ? 257 : 256);
-            if (t.total_tiles < split_below && pc.nt > 1 && !o.cls && !sw.on(SW_NO_SPLIT)) {
-                const int want = (256 + t.total_tiles - 1) / t.total_tiles;   // split factor that would fill the chip (narrow blocks: 512 measured level)
-                for (int nts = pc.nt / 2; nts >= 1; nts /= 2) {               // coarsest split first
-                    const TileCfg *c2 = tile_cfg_find_like(tp.cfg, nts);
-                    if (!c2) continue;
-                    cfg = c2;
-                    t.nsplit = pc.nt / nts;
-                    if (t.nsplit >= want) break;
-                }
-            }
-            t.grid = 8 * ((t.total_tiles + 7) / 8);   // one tile per workgroup, grid a multiple of the 8 XCDs
-            // split-K: when even the channel split leaves most CUs idle and the contraction is several channel-group
-            // stages deep, the stages are dealt to grid.z workgroups (fp32 partials, summed in fixed order by
-            // splitk_finish) so that one workgroup no longer walks all of them in sequence
-            t.ksplit = 1;
-            t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
-            float *partial = nullptr;
-            const int64_t M_out = (int64_t)out.B * No * Ho * Wo;
-            // transposed conv on few tiles: its 4 sub-pixel passes as 4 workgroups (no reduction, any epilogue)
-            const int thr = sw.split_wg;
-            t.pass_split = (L.transposed && t.total_tiles * t.nsplit <= thr && !sw.on(SW_NO_SPLITK)) ? 1 : 0;
-            if (t.pass_split && tp.nstage >= 2 && !sw.on(SW_NO_TEAMS)) {
-                // a transposed layer whose passes are workgroups of their own walks its 2-4 channel-group stages one after the other (SPP conv8 at batch 1:
-                // 30 us): one stage per team instead, with as few output-channel workgroups per tile as keep the launch to one round of workgroups
-                for (int nts = cfg->nt; nts <= pc.nt && nts <= 2; nts *= 2) {
-                    const TileCfg *team = tile_cfg_find_team(cfg, tp.nstage, nts);
-                    if (!team) continue;
-                    const int tz_t = (a.Ng + team->tz - 1) / team->tz, ty_t = (a.Hg + team->ty - 1) / team->ty, tx_t = (a.Wg + team->tx - 1) / team->tx;
-                    const int64_t wgs = (int64_t)a.B * tz_t * ty_t * tx_t * (pc.nt / nts) * 4;
-                    if (wgs > sw.team_max_wgs) continue;
-                    cfg = team;
-                    t.nsplit = pc.nt / nts;
-                    t.tiles_z = tz_t; t.tiles_y = ty_t; t.tiles_x = tx_t;
-                    t.total_tiles = a.B * tz_t * ty_t * tx_t;
-                    t.grid = 8 * ((t.total_tiles + 7) / 8);
-                    t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
-                    break;
-                }
-            }
-            if (!t.pass_split && tile_cfg_has_splitk(cfg) && t.total_tiles * t.nsplit <= thr * 3 / 4 && tp.nstage >= 2 && !o.cls && !o.out_pre && !o.outf && !o.discard && !o.res_bcast && L.cout % 4 == 0 &&
-                !sw.on(SW_NO_SPLITK)) {
-                // enough splits for ~two workgroups per CU (measured 256 ... 768 at batch 1 / 4 and on one End_to_End stack: 512 is 3-4 %
-                // faster than the earlier floor(256 / n), which left 129 ... 192-workgroup launches unsplit)
-                const int want = (sw.ksplit_target + t.total_tiles * t.nsplit - 1) / (t.total_tiles * t.nsplit);
-                t.ksplit = std::max(1, std::min(std::min(tp.nstage, want), 8));
-                // the same split INSIDE the workgroup where a team configuration covers it (round 6): the teams' partial sums meet in LDS, no partials through
-                // memory and no splitk_finish launch (5-6 us each behind 28 of a batch-1 forward's 89 launches)
-                const TileCfg *team = (t.ksplit > 1 && !sw.on(SW_NO_TEAMS)) ? tile_cfg_find_team(cfg, tp.nstage, cfg->nt) : nullptr;
-                if (team) {
-                    // ... unless the team launch needs several rounds of workgroups (their LDS images allow one or two per CU, and next to the other streams'
-                    // kernels they take whole CUs): measured per layer at batch 1 / 2 / 4, profiles/r06_batch1_teams.txt
-                    const int tz_t = (a.Ng + team->tz - 1) / team->tz;
-                    const int64_t wgs = (int64_t)a.B * tz_t * ((a.Hg + team->ty - 1) / team->ty) * ((a.Wg + team->tx - 1) / team->tx) * t.nsplit;
-                    if (wgs < sw.team_min_wgs || wgs > sw.team_max_wgs) team = nullptr;
-                }
-                if (team) {
-                    cfg = team;
-                    t.ksplit = 1;
-                    t.tiles_z = (a.Ng + cfg->tz - 1) / cfg->tz;
-                    t.tiles_y = (a.Hg + cfg->ty - 1) / cfg->ty;
-                    t.tiles_x = (a.Wg + cfg->tx - 1) / cfg->tx;
-                    t.total_tiles = a.B * t.tiles_z * t.tiles_y * t.tiles_x;
-                    t.grid = 8 * ((t.total_tiles + 7) / 8);
-                    t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
-                }
-                if (t.ksplit > 1) {
-                    t.partial_stride = M_out * (int64_t)pc.nt * 16;
-                    partial = (float *)raw(t.ksplit * t.partial_stride * (int64_t)sizeof(float));
-                    t.partial = partial;
-                    if (!ok()) return out;
-                }
-            }
-            if (dry) {
-                drop_raw(partial);
-                return out;
-            }
-            // the pixel-pair stem on whole tiles from the fp32 stack: the persistent pipelined kernel (dffw_stem.hip)
-            const bool tracing = sw.trace_layer && sw.trace_out && name == sw.trace_layer;   // stem_pipe has no tile timeline: a traced stem runs on conv_tile
-            const bool stem_pipe_run = stem_pair && !sw.on(SW_NO_STEM_PIPE) && !tracing && stem_pipe_ok(e->prec, cfg, a, t);
-            auto kernel_name = [&](char *kn, int n) {
-                if (stem_pipe_run) return stem_pipe_kernel_name(a, kn, n);
-                conv_tile_kernel_name(e->prec, cfg, t.ksplit > 1 || (a.dbg & (DFFW_ARGS_RAW | DFFW_ARGS_SUMS)), tile_lean(e->prec, cfg, a, t), kn, n);
-            };
-            {
-                char kn[96];
-                kernel_name(kn, sizeof kn);
-                g_last_kernel = kn;
-            }
-            if (e->profiling) {
-                char kn[96];
-                kernel_name(kn, sizeof kn);
-                const double opx = (double)out.B * No * Ho * Wo;
-                const double bytes = (double)in0.pixels() * L.cin * elem_bytes()
-                                     + opx * L.cout * (o.outf ? 4.0 : elem_bytes() * (o.out_pre ? 2 : 1))
-                                     + opx * L.cout * elem_bytes() * ((o.res0 ? 1 : 0) + (o.res1 ? 1 : 0))
-                                     + (double)L.kd * L.kh * L.kw * L.cin * L.cout * elem_bytes();
-                prof_begin(kn, name, flops, bytes);
-            }
-            // debug timeline of one layer: DFFW_TRACE_LAYER=<layer name> DFFW_TRACE_OUT=<file>; per tile 8 x u64
-            // (s_memtime at start / fill issued / fill landed / contraction done / stores acknowledged, HW_ID)
-            unsigned long long *trace = nullptr;
-            const char *tl = sw.trace_layer, *tout = sw.trace_out;
-            if (tl && tout && name == tl) {
-                check(hipMalloc((void **)&trace, (size_t)t.total_tiles * 64), "trace alloc");
-                if (ok()) check(hipMemsetAsync(trace, 0, (size_t)t.total_tiles * 64, s), "trace memset");
-                a.trace = trace;
-            }
-            check(stem_pipe_run ? launch_stem_pipe(a, t, sw.roll_wgs, s) : launch_conv_tile(e->prec, cfg, a, t, s), name.c_str());
-            prof_end();
-            if (t.ksplit > 1) {
-                prof_begin("dffw::splitk_finish_kernel", name + " (split-K finish)", 0.0,
-                           (double)M_out * L.cout * (4.0 * t.ksplit + elem_bytes() * (o.res0 ? 2 : 1)));
-#ifndef DFFW_EXP_SKIP_FINISH   // (dev-only timing bound, tools/build_variant_lib.sh: what a split-K without its finish launch could save at most; results are garbage)
-                check(launch_splitk_finish(e->prec, partial, t.ksplit, t.partial_stride, M_out, pc.nt * 16, L.cout, pc.bias, a.res0,
-                                           o.relu, out.p, s), "splitk_finish");
+#ifdef DFFW_TRACE_BUILD
+constexpr size_t SRD_TRACE_WORDS = Run::STEP_TRACE_WORDS;
+#else
+constexpr size_t SRD_TRACE_WORDS = 0;   // (the production srd kernels write no step timeline)
 #endif
-                prof_end();
-                drop_raw(partial);
-            }
-            if (trace && ok()) {
-                std::vector<unsigned long long> host((size_t)t.total_tiles * 8);
-                check(hipStreamSynchronize(s), "trace sync");
-                check(hipMemcpy(host.data(), trace, host.size() * 8, hipMemcpyDeviceToHost), "trace copy");
-                if (FILE *f = fopen(tout, "wb")) {
-                    fwrite(host.data(), 8, host.size(), f);
-                    fclose(f);
-                }
-                (void)hipFree(trace);
-            }
-            return out;
-        }
-        if (dry) return out;
-        for (const Variant &v : pc.variants) {
-            a.KC = v.KC;
-            a.tab = v.tab;
-            a.wpk = v.wpk;
-            if (L.transposed) {
-                a.Ng = in0.N; a.Hg = in0.H; a.Wg = in0.W;
-                a.sy = a.sx = 1;
-                a.osy = a.osx = 2;
-                a.ooy = v.ooy; a.oox = v.oox;
-            } else {
-                a.Ng = No; a.Hg = Ho; a.Wg = Wo;
-                a.sy = L.sh; a.sx = L.sw;
-                a.osy = a.osx = 1;
-                a.ooy = a.oox = 0;
-            }
-            a.M = (int64_t)a.B * a.Ng * a.Hg * a.Wg;
-            if (sw.on(SW_NO_SMALL)) a.dbg |= 32;   // (bit 5 of dbg: conv_igemm also for small grids)
-            {
-                char kn[64];
-                conv_kernel_name_for(e->prec, a, kn, sizeof kn);
-                g_last_kernel = kn;
-            }
-            if (e->profiling) {
-                char kn[64];
-                conv_kernel_name_for(e->prec, a, kn, sizeof kn);
-                const double nv = (double)pc.variants.size();
-                const double opx = (double)a.M;  // output pixels written by this launch
-                double bytes = (double)in0.pixels() * L.cin * elem_bytes() / nv   // input volume read once per layer
-                               + opx * L.cout * (o.outf ? 4.0 : elem_bytes() * (o.out_pre ? 2 : 1))
-                               + opx * L.cout * elem_bytes() * ((o.res0 ? 1 : 0) + (o.res1 ? 1 : 0))
-                               + (double)v.ntaps * L.cin * L.cout * elem_bytes();
-                prof_begin(kn, name, 2.0 * (double)a.M * v.ntaps * L.cin * L.cout, bytes);
-            }
-            check(launch_conv(e->prec, a, s), name.c_str());
-            prof_end();
-        }
-        return out;
-    }
-
-    Act pool(const Act &x, int mode, int k) {
-        Act out = act(x.B, x.N, x.H / k, x.W / k, x.C);
-        if (ok() && !dry) {
-            char kn[48];
-            snprintf(kn, sizeof kn, "dffw::pool_kernel<%d>", e->prec);
-            prof_begin(kn, mode == 0 ? "maxpool" : "avgpool", 0.0, (double)(x.pixels() + out.pixels()) * x.C * elem_bytes());
-            check(launch_pool(e->prec, mode, k, x.p, out.p, x.B, x.N, x.H, x.W, x.C, s), "pool");
-            prof_end();
-        }
-        return out;
-    }
-
-    void tap(const char *name, const Act &a) {
-        if (!ok() || dry) return;
-        for (int i = 0; i < n_taps; ++i)
-            if (!strcmp(taps[i].name, name)) {
-                const int64_t n = a.pixels() * a.C;
-                if (taps[i].numel != n) {
-                    err = fail(DFFW_EINVAL, "tap %s holds %lld elements, caller gave %lld", name, (long long)n, (long long)taps[i].numel);
-                    return;
-                }
-                check(launch_to_ncdhw(e->prec, a.p, taps[i].dst, a.B, a.C, a.N, a.H, a.W, s), name);
-            }
-    }
-    void tap_f32(const char *name, const float *p, int64_t n) {
-        if (!ok() || dry) return;
-        for (int i = 0; i < n_taps; ++i)
-            if (!strcmp(taps[i].name, name)) {
-                if (taps[i].numel != n) {
-                    err = fail(DFFW_EINVAL, "tap %s holds %lld elements, caller gave %lld", name, (long long)n, (long long)taps[i].numel);
-                    return;
-                }
-                check(hipMemcpyAsync(taps[i].dst, p, n * sizeof(float), hipMemcpyDeviceToDevice, s), name);
-            }
-    }
-};
 
 // SRD block (DEN.py:317-330): x -> feat = relu(x + BN(conv(relu(BN(conv x))))) ; feat + relu(conv1(relu(conv3x1x1 feat)))
 // pooled (optional): receives max_pool(1,2,2) of the block's output when the fused attention kernel can produce it
@@ -1350,15 +253,14 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
                 if (pipe16) srd_pipe16_kernel_name(r.e->prec, with_pool, kn, sizeof kn);
                 else if (x.C == 16) srd_roll16_kernel_name(r.e->prec, with_pool, kn, sizeof kn);
                 else srd_roll_kernel_name(r.e->prec, with_pool, kn, sizeof kn);
-                g_last_kernel = kn;
                 const double px = (double)x.pixels();
                 // algorithmic: two 1x3x3 C -> C convs + the 3x1x1 and 1x1x1 attention convs; x read once, out (+ pooled) written once
-                r.prof_begin(kn, p, 2.0 * px * (2 * 9 + 4) * x.C * x.C, (with_pool ? 2.25 : 2.0) * px * x.C * r.elem_bytes());
+                r.launch(kn, p, "", 2.0 * px * (2 * 9 + 4) * x.C * x.C, (with_pool ? 2.25 : 2.0) * px * x.C * r.elem_bytes(), "srd_roll", SRD_TRACE_WORDS, [&](unsigned long long *trace) {
 #ifdef DFFW_TRACE_BUILD
-                a.trace = r.trace_begin(p, 1024, 4);
+                    a.trace = trace;
 #endif
-                r.check(pipe16 ? launch_srd_pipe16(r.e->prec, a, r.s) : x.C == 16 ? launch_srd_roll16(r.e->prec, a, r.s) : launch_srd_roll(r.e->prec, a, r.s), "srd_roll");
-                r.prof_end();
+                    return pipe16 ? launch_srd_pipe16(r.e->prec, a, r.s) : x.C == 16 ? launch_srd_roll16(r.e->prec, a, r.s) : launch_srd_roll(r.e->prec, a, r.s);
+                });
                 r.trace_end();
             }
             if (drop_x) r.drop(x);
@@ -1413,100 +315,68 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
 
 // EFD block (DEN.py:306-315)
 static Act efd(Run &r, const std::string &p, const Act &x, Act *pooled = nullptr) {
+    auto ca = r.e->convs.find(p + ".stride_conv.0"), cb = r.e->convs.find(p + ".max_pooling.1.0");
+    const int Ho = x.H / 2, Wo = x.W / 2;
+    const double opx = (double)x.B * x.N * Ho * Wo;
+    // a fused block serves the shape: its pooled input is at hand, both layers are packed, whole ty x tx columns of the output grid that fill the chip
+    auto fused = [&](int C, int ty, int tx) {
+        return x.C == C && pooled && pooled->p && ca != r.e->convs.end() && cb != r.e->convs.end() && x.H % 2 == 0 && x.W % 2 == 0 && Ho % ty == 0 && Wo % tx == 0 &&
+               (int64_t)x.B * (Ho / ty) * (Wo / tx) >= r.sw.roll_min_units && !r.sw.on(SW_NO_ROLL) && !r.sw.on(SW_NO_FUSED_EFD) && !r.sw.on(SW_NO_TILE);
+    };
+    auto args = [&](int cout, uint16_t *out) {   // a.in0 = x, a.in1 = its (1,2,2) max-pool
+        ConvArgs a;
+        memset(&a, 0, sizeof a);
+        a.in0 = x.p; a.C0 = x.C;
+        a.in1 = pooled->p; a.C1 = x.C;
+        a.B = x.B; a.Ni = x.N; a.Hi = x.H; a.Wi = x.W;
+        a.Ng = x.N; a.Hg = Ho; a.Wg = Wo;
+        a.No = x.N; a.Ho = Ho; a.Wo = Wo;
+        a.Cout = cout;
+        a.bias = ca->second.bias;
+        a.out = out;
+        a.relu = 1;
+        a.M = (int64_t)x.B * x.N * Ho * Wo;
+        return a;
+    };
+    int ty, tx;
     // the 8 -> 16 channel block with its pooled input at hand: both branches in one rolling kernel (conv_roll_efd)
-    {
-        auto ca = r.e->convs.find(p + ".stride_conv.0"), cb = r.e->convs.find(p + ".max_pooling.1.0");
-        int ty, tx;
-        efd_roll_tile(&ty, &tx);
-        const int Ho = x.H / 2, Wo = x.W / 2;
-        const auto end = r.e->convs.end();
-        if (x.C == 8 && pooled && pooled->p && ca != end && cb != end && ca->second.wroll8 && cb->second.wroll8 && x.H % 2 == 0 && x.W % 2 == 0 &&
-            Ho % ty == 0 && Wo % tx == 0 && (int64_t)x.B * (Ho / ty) * (Wo / tx) >= r.sw.roll_min_units && !r.sw.on(SW_NO_ROLL) &&
-            !r.sw.on(SW_NO_FUSED_EFD) && !r.sw.on(SW_NO_TILE)) {
-            Act out = r.act(x.B, x.N, Ho, Wo, 16);
+    efd_roll_tile(&ty, &tx);
+    if (fused(8, ty, tx) && ca->second.wroll8 && cb->second.wroll8) {
+        Act out = r.act(x.B, x.N, Ho, Wo, 16);
+        if (r.ok() && !r.dry) {
+            if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return out; }
+            ConvArgs a = args(16, out.p);
+            a.zero = r.e->zero_page;
+            a.dbg = (r.sw.debug_flags & 6) | r.sw.path_bits();
+            RollArgs t = roll_args(ca->second.wroll8, x.B, Ho / ty, Wo / tx, 1, r.sw.roll_wgs);
+            t.wroll2 = cb->second.wroll8;
+            t.bias2 = cb->second.bias;
+            char kn[64];
+            conv_roll_efd_kernel_name(r.e->prec, a, true, kn, sizeof kn);
+            r.launch(kn, p, "", 2.0 * opx * 27.0 * 8 * 16 * 2, ((double)x.pixels() * 8 + opx * 8 + opx * 16) * r.elem_bytes(), "conv_roll_efd", 0,
+                     [&](unsigned long long *) { return launch_conv_roll_efd(r.e->prec, a, t, r.s); });
+        }
+        r.drop(*pooled);
+        return out;
+    }
+    // the 16 -> 32 channel block (`FM_conv2.0`): both branches in one streaming kernel, the waves split by branch / output tile / pixel half (conv_efd16)
+    efd16_tile(&ty, &tx);
+    if (fused(16, ty, tx) && ca->second.wroll_s2 && cb->second.wroll15 && ca->second.def.cout == 32) {
+        ConvArgs a = args(32, (uint16_t *)16);   // (a placeholder output for the check below: the output is allocated once the kernel is known to serve the shape)
+        RollArgs t = roll_args(ca->second.wroll_s2, x.B, Ho / ty, Wo / tx, 1, r.sw.roll_wgs);
+        t.wroll2 = cb->second.wroll15;
+        t.bias2 = cb->second.bias;
+        if (efd16_ok(r.e->prec, a, t)) {
+            Act out = r.act(x.B, x.N, Ho, Wo, 32);
             if (r.ok() && !r.dry) {
-                if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return out; }
-                ConvArgs a;
-                memset(&a, 0, sizeof a);
-                a.in0 = x.p; a.C0 = 8;
-                a.in1 = pooled->p; a.C1 = 8;
-                a.B = x.B; a.Ni = x.N; a.Hi = x.H; a.Wi = x.W;
-                a.Ng = x.N; a.Hg = Ho; a.Wg = Wo;
-                a.No = x.N; a.Ho = Ho; a.Wo = Wo;
-                a.Cout = 16;
-                a.bias = ca->second.bias;
                 a.out = out.p;
-                a.relu = 1;
-                a.zero = r.e->zero_page;
-                a.M = (int64_t)x.B * x.N * Ho * Wo;
-                a.dbg = (r.sw.debug_flags & 6) | r.sw.path_bits();
-                RollArgs t;
-                memset(&t, 0, sizeof t);
-                t.wroll = ca->second.wroll8;
-                t.wroll2 = cb->second.wroll8;
-                t.bias2 = cb->second.bias;
-                t.tiles_y = Ho / ty; t.tiles_x = Wo / tx;
-                t.zsplit = 1;
-                t.total_tiles = x.B * t.tiles_y * t.tiles_x;
-                t.wgs = r.sw.roll_wgs;
                 char kn[64];
-                conv_roll_efd_kernel_name(r.e->prec, a, true, kn, sizeof kn);
-                g_last_kernel = kn;
-                const double opx = (double)x.B * x.N * Ho * Wo;
-                r.prof_begin(kn, p, 2.0 * opx * 27.0 * 8 * 16 * 2, ((double)x.pixels() * 8 + opx * 8 + opx * 16) * r.elem_bytes());
-                r.check(launch_conv_roll_efd(r.e->prec, a, t, r.s), "conv_roll_efd");
-                r.prof_end();
+                conv_efd16_kernel_name(kn, sizeof kn);
+                r.launch(kn, p, "", 2.0 * opx * 27.0 * 16 * 32 * 2, ((double)x.pixels() * 16 + opx * 16 + opx * 32) * r.elem_bytes(), "conv_efd16", 0,
+                         [&](unsigned long long *) { return launch_conv_efd16(a, t, r.s); });
             }
             r.drop(*pooled);
             return out;
-        }
-    }
-    // the 16 -> 32 channel block (`FM_conv2.0`): both branches in one streaming kernel, the waves split by branch / output tile / pixel half (conv_efd16)
-    {
-        auto ca = r.e->convs.find(p + ".stride_conv.0"), cb = r.e->convs.find(p + ".max_pooling.1.0");
-        int ty, tx;
-        efd16_tile(&ty, &tx);
-        const int Ho = x.H / 2, Wo = x.W / 2;
-        const auto end = r.e->convs.end();
-        if (x.C == 16 && pooled && pooled->p && ca != end && cb != end && ca->second.wroll_s2 && cb->second.wroll15 && ca->second.def.cout == 32 && x.H % 2 == 0 &&
-            x.W % 2 == 0 && Ho % ty == 0 && Wo % tx == 0 && (int64_t)x.B * (Ho / ty) * (Wo / tx) >= r.sw.roll_min_units && !r.sw.on(SW_NO_ROLL) &&
-            !r.sw.on(SW_NO_FUSED_EFD) && !r.sw.on(SW_NO_TILE)) {
-            ConvArgs a;
-            memset(&a, 0, sizeof a);
-            a.in0 = x.p; a.C0 = 16;
-            a.in1 = pooled->p; a.C1 = 16;
-            a.B = x.B; a.Ni = x.N; a.Hi = x.H; a.Wi = x.W;
-            a.Ng = x.N; a.Hg = Ho; a.Wg = Wo;
-            a.No = x.N; a.Ho = Ho; a.Wo = Wo;
-            a.Cout = 32;
-            a.bias = ca->second.bias;
-            a.relu = 1;
-            a.M = (int64_t)x.B * x.N * Ho * Wo;
-            RollArgs t;
-            memset(&t, 0, sizeof t);
-            t.wroll = ca->second.wroll_s2;
-            t.wroll2 = cb->second.wroll15;
-            t.bias2 = cb->second.bias;
-            t.tiles_y = Ho / ty; t.tiles_x = Wo / tx;
-            t.zsplit = 1;
-            t.total_tiles = x.B * t.tiles_y * t.tiles_x;
-            t.wgs = r.sw.roll_wgs;
-            a.out = (uint16_t *)16;   // (placeholder for the check below: the output is allocated once the kernel is known to serve the shape)
-            if (efd16_ok(r.e->prec, a, t)) {
-                Act out = r.act(x.B, x.N, Ho, Wo, 32);
-                if (r.ok() && !r.dry) {
-                    a.out = out.p;
-                    char kn[64];
-                    conv_efd16_kernel_name(kn, sizeof kn);
-                    g_last_kernel = kn;
-                    const double opx = (double)x.B * x.N * Ho * Wo;
-                    r.prof_begin(kn, p, 2.0 * opx * 27.0 * 16 * 32 * 2, ((double)x.pixels() * 16 + opx * 16 + opx * 32) * r.elem_bytes());
-                    r.check(launch_conv_efd16(a, t, r.s), "conv_efd16");
-                    r.prof_end();
-                }
-                r.drop(*pooled);
-                return out;
-            }
         }
     }
     Act a = r.conv(p + ".stride_conv.0", x);

@@ -89,6 +89,8 @@ def _load():
                                     POINTER(c_int64), c_void_p, c_void_p]
     c_u8p = POINTER(ctypes.c_uint8)
     lib.dffw_pack_stack.argtypes = [c_int, c_void_p, c_int, POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.dffw_augment_stack.argtypes = [c_int, c_void_p, c_int, POINTER(c_int64)] + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 6 + \
+                                      [c_int, c_float, c_float, c_float, c_void_p]
     lib.dffw_unpack_stack.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.dffw_colorize.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]
     lib.dffw_jet_lut.argtypes = [c_u8p]
@@ -117,6 +119,7 @@ def _load():
 lib = _load()
 COMM_ID_BYTES = 128
 RAW_NORM_F64 = 16   # DFFW_RAW_NORM_F64: the FS6 loader's float64 normalisation
+AUG_NPARAMS = 8     # DFFW_AUG_NPARAMS: crop row, crop col, contrast, brightness, gamma, flip_x, flip_y, angle
 
 # every symbol include/dffw.h declares (tests check the library exports each one)
 ABI_SYMBOLS = (
@@ -125,7 +128,7 @@ ABI_SYMBOLS = (
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
     "dffw_op_of_block",
-    "dffw_forward_raw", "dffw_pack_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
+    "dffw_forward_raw", "dffw_pack_stack", "dffw_augment_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
     "dffw_sim_workspace_bytes", "dffw_sim_render", "dffw_sim_plan_host", "dffw_sim_disk_rows",

@@ -2,13 +2,14 @@
 reference's loaders and scripts do in NumPy around `model(FS, focus_dists)`.
 
     FS = pack_stack(raw_u8, "NHWC")                       # test_Dataloader.py:121-141: /127.5-1, transpose, pad to x32 with -1
+    FS, gt, mask = augment_stack(raw_u8, "HWCN", gt=gt, **train_seeds(rng, B))   # train_Dataloader.py + augmentation.py: a training sample
     fd = focus_dists(values, B)                           # (B,N,1,1): broadcast instead of np.tile(..., [1,H,W]) (test_Dataloader.py:24)
     _, _, _, pred3 = model(FS, fd)
     rgb = colorize(pred3, size=(H, W), vrange=(lo, hi))   # test.py:124-133;  vrange=None: test_real_scenes.py:40-52
     m = masked_metrics(pred3, gt, mask)                   # metrics.py:90-127 as called from test.py:144-158
 
-Everything stays in device memory; the kernels live in libdffw.so (csrc/dffw_io.hip) and are reached through the C ABI
-(include/dffw.h: dffw_pack_stack, dffw_colorize, dffw_metrics).  No CPU fallback: CPU tensors raise."""
+Everything stays in device memory; the kernels live in libdffw.so (csrc/dffw_io.hip, csrc/dffw_aug.hip) and are reached through the C ABI
+(include/dffw.h: dffw_pack_stack, dffw_augment_stack, dffw_colorize, dffw_metrics).  No CPU fallback: CPU tensors raise."""
 from ctypes import c_void_p, c_int64
 
 import numpy as np
@@ -71,6 +72,127 @@ def pack_stack(raw, layout="NHWC", crop=None, multiple=32, norm="f32"):
         _check(lib.dffw_pack_stack(dev, c_void_p(raw.data_ptr() + off), (0 if raw.dtype == torch.uint8 else 1) | nflag, strides, B, N, h, w,
                                    Hp, Wp, c_void_p(FS.data_ptr()), _stream_ptr(dev)), "dffw_pack_stack")
     return FS
+
+
+def train_seeds(rng, batch, cropping=None):
+    """The random draws of the training loaders' get_seeds() (train_Dataloader.py:80,141,215,268,379) for `batch` samples, in the
+    reference's order, from a random.Random (or the random module): with cropping=(cy, cx) first randint(0, cy-1), randint(0, cx-1),
+    then uniform(0.4,1.6), uniform(-0.1,0.1), uniform(0.5,2.0), uniform(0,1), uniform(0,1), randint(0,3).  Returns the keyword
+    arguments of augment_stack as a dict of per-sample lists (crop: (y0, x0) pairs; the caller adds size=)."""
+    out = {k: [] for k in ((("crop",) if cropping is not None else ()) + ("contrast", "brightness", "gamma", "flip_x", "flip_y", "angle"))}
+    for _ in range(batch):
+        if cropping is not None:
+            y0 = rng.randint(0, cropping[0] - 1)
+            out["crop"].append((y0, rng.randint(0, cropping[1] - 1)))
+        out["contrast"].append(rng.uniform(0.4, 1.6))
+        out["brightness"].append(rng.uniform(-0.1, 0.1))
+        out["gamma"].append(rng.uniform(0.5, 2.0))
+        out["flip_x"].append(rng.uniform(0, 1.0))
+        out["flip_y"].append(rng.uniform(0, 1.0))
+        out["angle"].append(rng.randint(0, 3))
+    return out
+
+
+def _per_sample(v, B, what):
+    """One float per sample from a scalar, a sequence of length B (or 1) or a tensor (a device tensor is read back: one
+    synchronisation; pass host values to stay enqueue-only)."""
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().reshape(-1).tolist()
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, B)
+    if a.size != B:
+        raise ValueError(f"{what}: expected one value or {B}, got {a.size}")
+    return a
+
+
+def augment_stack(raw, layout="NHWC", *, contrast, brightness, gamma, flip_x, flip_y, angle, crop=None, size=None, norm="f32",
+                  gt=None, conf=None, gt_range=None, sentinel=0.0):
+    """What the reference's training loaders do to a decoded sample (train_Dataloader.py with augmentation.py): crop, the photometric
+    chain image_augmentation(x, contrast, brightness, gamma), horizontal flip (flip_x > 0.5), vertical flip (flip_y > 0.5), np.rot90 by
+    `angle` quarter turns, the ground-truth range rule and the transpose to (3,N,h,w) float32, on the GPU.
+
+    raw: as for pack_stack (uint8 or float32 0..255, `layout`, optional batch dim, any strides).  contrast ... angle: one value per
+    sample (scalar, sequence of length B, or tensor); the flips take the loaders' uniform draws or booleans.  crop: (y0, x0) for all or
+    one pair per sample, with size=(h, w) the window (default: the whole image).  norm: "f32" for the loaders that hold float32 arrays
+    (DDFF, HCI, Smartphone), "f64" for FS6 / FlyingThings (float64 chain, rounded once).
+    Returns FS float32 (B,3,N,h',w') with (h',w') = (h,w), or (w,h) for odd angles (h != w: all angles of a batch need one parity).
+    gt / conf: float (B,H,W) at source size.  Then returns (FS, gt, mask[, conf]) in the same crop and pose: gt float32 with values
+    < gt_range[0] or > gt_range[1] set to `sentinel` (gt_range=None: no rule), mask bool = (gt != sentinel) (NaN counts as valid)."""
+    nflag = _norm_flag(norm)
+    if layout not in _LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r} (one of {sorted(_LAYOUTS)})")
+    dev = _dev(raw, "raw stack")
+    if raw.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"raw stack must be uint8 or float32, got {raw.dtype}")
+    if raw.dim() == 4:
+        raw = raw.unsqueeze(0)
+    if raw.dim() != 5:
+        raise ValueError(f"raw stack must have 4 or 5 dims, got {tuple(raw.shape)}")
+    an, ay, ax, ac = (1 + a for a in _LAYOUTS[layout])
+    if raw.shape[ac] != 3:
+        raise ValueError(f"layout {layout}: expected 3 colour channels on axis {ac}, got {raw.shape[ac]}")
+    B, N, H, W = raw.shape[0], raw.shape[an], raw.shape[ay], raw.shape[ax]
+    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if h < 1 or w < 1 or h > H or w > W:
+        raise ValueError(f"window {h}x{w} does not fit the {H}x{W} source")
+    if isinstance(crop, torch.Tensor):
+        crop = crop.detach().cpu().tolist()
+    origin = np.asarray((0, 0) if crop is None else crop, dtype=np.int64).reshape(-1, 2)
+    if origin.shape[0] == 1:
+        origin = np.repeat(origin, B, axis=0)
+    if origin.shape[0] != B:
+        raise ValueError(f"crop: expected one (y0, x0) pair or {B}, got {origin.shape[0]}")
+    if (origin < 0).any() or (origin[:, 0] + h > H).any() or (origin[:, 1] + w > W).any():
+        raise ValueError(f"crop {origin.tolist()} with window {h}x{w} does not fit the {H}x{W} source")
+    rec = np.empty((B, engine.AUG_NPARAMS), dtype=np.float64)
+    rec[:, 0:2] = origin
+    for k, (v, what) in enumerate(((contrast, "contrast"), (brightness, "brightness"), (gamma, "gamma"), (flip_x, "flip_x"),
+                                   (flip_y, "flip_y"), (angle, "angle")), start=2):
+        rec[:, k] = _per_sample(v, B, what)
+    turns = rec[:, 7]
+    if (turns != np.floor(turns)).any():
+        raise ValueError(f"angle must be whole quarter turns, got {turns.tolist()}")
+    rec[:, 7] = turns = np.mod(turns, 4)
+    odd = (turns.astype(np.int64) & 1).astype(bool)
+    if h != w and odd.any() and not odd.all():
+        raise ValueError(f"a batch with a {h}x{w} window needs angles of one parity (the output has one shape), got {turns.tolist()}")
+    transposed = bool(odd.all())
+    oh, ow = (w, h) if transposed else (h, w)
+    labels = []
+    for name, t in (("gt", gt), ("conf", conf)):
+        if t is None:
+            labels.append(None)
+            continue
+        if _dev(t, name) != dev:
+            raise ValueError(f"{name} is on another device")
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        if tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{name} must be ({B}, {H}, {W}) like the source, got {tuple(t.shape)}")
+        labels.append(t.to(torch.float32).contiguous())
+    gt32, conf32 = labels
+    if conf32 is not None and gt32 is None:
+        raise ValueError("conf needs gt")
+    lo, hi = (-np.inf, np.inf) if gt_range is None else (-np.inf if gt_range[0] is None else gt_range[0], np.inf if gt_range[1] is None else gt_range[1])
+    params = torch.from_numpy(rec).to(raw.device)
+    st = raw.stride()
+    strides = (c_int64 * 5)(st[0], st[an], st[ay], st[ax], st[ac])
+    FS = torch.empty((B, 3, N, oh, ow), dtype=torch.float32, device=raw.device)
+    gt_out = mask = conf_out = None
+    if gt32 is not None:
+        gt_out = torch.empty((B, oh, ow), dtype=torch.float32, device=raw.device)
+        mask = torch.empty((B, oh, ow), dtype=torch.bool, device=raw.device)
+    if conf32 is not None:
+        conf_out = torch.empty((B, oh, ow), dtype=torch.float32, device=raw.device)
+    ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.dffw_augment_stack(dev, c_void_p(raw.data_ptr()), (0 if raw.dtype == torch.uint8 else 1) | nflag, strides, B, N, H, W, h, w,
+                                      ptr(params), int(transposed), ptr(FS), ptr(gt32), ptr(conf32), ptr(gt_out), ptr(mask), ptr(conf_out),
+                                      0 if gt_range is None else 1, float(np.float32(lo)), float(np.float32(hi)), float(np.float32(sentinel)),
+                                      _stream_ptr(dev)), "dffw_augment_stack")
+    if gt32 is None:
+        return FS
+    return (FS, gt_out, mask) + ((conf_out,) if conf32 is not None else ())
 
 
 def focus_dists(values, batch=1, device="cuda"):

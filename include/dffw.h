@@ -191,7 +191,7 @@ int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, 
                      const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y,
                      void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_sim_render call, in launch order, joined by
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 
@@ -230,6 +230,30 @@ int dffw_op_fov_warp(int device, const float *x, int B, int C, int N, int H, int
 #define DFFW_RAW_NORM_F64 16 /* flag OR-ed into dtype: normalise in float64, round once (the FS6 loader) */
 int dffw_pack_stack(int device, const void *raw, int dtype, const int64_t strides[5], int B, int N, int h, int w,
                     int Hp, int Wp, float *FS, void *hip_stream);
+
+/* ---- training-sample assembly (train_codes/train_Dataloader.py with train_codes/augmentation.py) ---------------
+ * What the reference's five training loaders do to a decoded sample: random crop to the training size, the photometric chain
+ * image_augmentation (x/255, (0.5 + contrast*(x-0.5)) + brightness, clamp to [0,1], np.power(x, gamma), clamp, x/0.5 - 1.0),
+ * horizontal flip, vertical flip, np.rot90, the ground-truth range rule with its mask, and the transpose to (3,N,h,w) float32.
+ * Every arithmetic step is one IEEE operation in the reference's order, in float32 (sources the loaders hold as float32: DDFF,
+ * HCI, Smartphone) or, with DFFW_RAW_NORM_F64, in float64 rounded once at the end (FS6, FlyingThings); the power is evaluated in
+ * double in both.  With gamma == 1 the result is bit-identical to NumPy's; otherwise within 2^-22 absolute.
+ *   raw / dtype / strides   as for dffw_pack_stack, but `raw` points at the WHOLE (H, W) source: the crop is per sample
+ *   h, w       window taken from every sample (h <= H, w <= W)
+ *   params     DEVICE fp64 (B, DFFW_AUG_NPARAMS), one record per sample in DFFW_AUG_* order: crop origin (row, col; clamped into
+ *              the source), contrast, brightness, gamma, flip_x and flip_y (flip if > 0.5: the loaders' uniform draws or 0 / 1),
+ *              angle (quarter turns, taken mod 4)
+ *   transposed 1 if the angles are odd: FS is (B,3,N,w,h) instead of (B,3,N,h,w).  Where h != w every sample's angle must have
+ *              this parity (its low bit is taken from here); where h == w angles may be mixed
+ *   FS         device fp32 (B,3,N,h',w'), no padding
+ *   gt, conf   device fp32 (B,H,W) contiguous, or NULL;  gt_out / conf_out fp32 (B,h',w'), mask_out uint8 (B,h',w') = (gt_out != sentinel).
+ *              use_range != 0: gt values < lo or > hi become `sentinel` first (float32 comparisons); NaN stays NaN and is valid.
+ * Enqueue-only on hip_stream, no allocation.  The kernel names are reported by dffw_last_op_kernels. */
+#define DFFW_AUG_NPARAMS 8
+enum { DFFW_AUG_Y0, DFFW_AUG_X0, DFFW_AUG_CONTRAST, DFFW_AUG_BRIGHTNESS, DFFW_AUG_GAMMA, DFFW_AUG_FLIP_X, DFFW_AUG_FLIP_Y, DFFW_AUG_ANGLE };
+int dffw_augment_stack(int device, const void *raw, int dtype, const int64_t strides[5], int B, int N, int H, int W, int h, int w,
+                       const double *params, int transposed, float *FS, const float *gt, const float *conf, float *gt_out,
+                       uint8_t *mask_out, float *conf_out, int use_range, float lo, float hi, float sentinel, void *hip_stream);
 
 /* dffw_forward on the raw stack: the stem kernel's loader applies `x/127.5 - 1` and the -1 padding while it stages its
  * tiles, so the normalised fp32 stack (4x the bytes of a uint8 source) is never written or read.  Bit-identical to

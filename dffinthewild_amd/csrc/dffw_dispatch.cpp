@@ -581,7 +581,8 @@ Act Run::conv(const std::string &name, const Act &in0, const ConvOpt &o) {
         return out;
     }
 
-    if (e->ensure_zero_page() != DFFW_OK) { err = DFFW_EHIP; return out; }
+    const uint16_t *zero = zero_page();
+    if (!zero) return out;
     if (p.clear_scores) check(hipMemsetAsync(o.cls_out, 0, (size_t)out.pixels() * 4, s), "score memset");
     // debug timeline of one layer (DFFW_TRACE_LAYER=<layer name> DFFW_TRACE_OUT=<file>): conv_tile writes 8 x u64 per tile (s_memtime at start / fill issued /
     // fill landed / contraction done / stores acknowledged, HW_ID), conv_roll its step timeline, the others none
@@ -590,7 +591,7 @@ Act Run::conv(const std::string &name, const Act &in0, const ConvOpt &o) {
     p.t.partial = partial;
     for (int i = 0; i < p.n; ++i) {
         ConvLaunch &l = p.l[i];
-        l.a.zero = e->zero_page;
+        l.a.zero = zero;
         launch(l.kernel, name, l.suffix, l.flops, l.bytes, name.c_str(), trace_words, [&](unsigned long long *trace) {
             l.a.trace = trace;
             if (f) return f->go(e->prec, l, s);
@@ -599,12 +600,12 @@ Act Run::conv(const std::string &name, const Act &in0, const ConvOpt &o) {
         });
     }
     if (partial) {
-        prof_begin("dffw::splitk_finish_kernel", name, 0.0, p.finish_bytes, " (split-K finish)");
-#if !(defined(DFFW_ABL_BUILD) && defined(DFFW_EXP_SKIP_FINISH))   // (dev-only timing bound, tools/build_variant_lib.sh: what a split-K without its finish launch could save at most; results are garbage)
-        check(launch_splitk_finish(e->prec, partial, p.t.ksplit, p.t.partial_stride, p.M_out, pc.nt * 16, L.cout, pc.bias, p.l[0].a.res0, o.relu, out.p, s),
-              "splitk_finish");
+        launch_unnamed("dffw::splitk_finish_kernel", name, " (split-K finish)", 0.0, p.finish_bytes, "splitk_finish", 0, [&](unsigned long long *) {
+#if defined(DFFW_ABL_BUILD) && defined(DFFW_EXP_SKIP_FINISH)   // (dev-only timing bound, tools/build_variant_lib.sh: what a split-K without its finish launch could save at most; results are garbage)
+            return hipSuccess;
 #endif
-        prof_end();
+            return launch_splitk_finish(e->prec, partial, p.t.ksplit, p.t.partial_stride, p.M_out, pc.nt * 16, L.cout, pc.bias, p.l[0].a.res0, o.relu, out.p, s);
+        });
         drop_raw(partial);
     }
     trace_end();

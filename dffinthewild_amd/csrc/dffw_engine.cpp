@@ -1,9 +1,8 @@
 // Host side of libdffw.so: the layer table (weight contract), BatchNorm folding + MFMA-fragment
 // weight packing, the static workspace arena and the whole-graph executor of DFF_net.forward
-// (reference Depth_Estimation_Test/Depth_Estimation_Network.py:74-127) and of the End_to_End variant
-// (End_to_End/End_to_End.py: alignment network + FOV warp in front of the same DFF_net), behind the C ABI
-// of include/dffw.h.  All arithmetic of the forward runs in the gfx950 kernels of dffw_kernels.hip;
-// nothing here touches activation values.
+// (reference Depth_Estimation_Test/Depth_Estimation_Network.py:74-127), behind the C ABI of include/dffw.h.
+// The End_to_End variant (End_to_End/End_to_End.py: alignment network + FOV warp in front of the same DFF_net)
+// is dffw_align.cpp.  All arithmetic of the forward runs in the gfx950 kernels; nothing here touches activation values.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -218,7 +217,7 @@ constexpr size_t SRD_TRACE_WORDS = 0;   // (the production srd kernels write no 
 // pooled (optional): receives max_pool(1,2,2) of the block's output when the fused attention kernel can produce it
 // on the way (else it is left empty and the caller pools separately).
 static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = nullptr) {
-    // the 8-channel block on whole 8 x 16 columns: one fused persistent kernel (dffw_srd_roll.hip)
+    // the 8- / 16-channel block on whole 8 x 16 / 4 x 16 columns: one fused persistent kernel (dffw_srd_roll.hip)
     {
         auto c0 = r.e->convs.find(p + ".Focus_Measure.conv.0.0"), c2 = r.e->convs.find(p + ".Focus_Measure.conv.2.0");
         auto a3 = r.e->convs.find(p + ".N_ch_attention.0"), a1 = r.e->convs.find(p + ".N_ch_attention.2");
@@ -235,19 +234,11 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
             const bool with_pool = pooled && !r.sw.on(SW_NO_FUSED_POOL);
             if (with_pool) *pooled = r.act(x.B, x.N, x.H / 2, x.W / 2, x.C);
             if (r.ok() && !r.dry) {
-                if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return out; }
-                SrdArgs a;
-                memset(&a, 0, sizeof a);
-                a.x = x.p; a.out = out.p; a.pooled = with_pool ? pooled->p : nullptr;
-                a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd;
-                a.b0 = c0->second.bias; a.b2 = c2->second.bias;
+                SrdArgs a = srd_args(x.p, out.p, c0->second, c2->second, x.B, x.N, x.H, x.W, sty, stx, r.sw.srd_wgs);
+                if (!(a.zero = r.zero_page())) return out;
+                a.pooled = with_pool ? pooled->p : nullptr;
                 a.w3 = a3->second.w32; a.w1 = a1->second.w32;
                 a.w3f = a3->second.watt; a.w1f = a1->second.watt;
-                a.zero = r.e->zero_page;
-                a.B = x.B; a.N = x.N; a.H = x.H; a.W = x.W;
-                a.tiles_y = x.H / sty; a.tiles_x = x.W / stx;
-                a.total_tiles = x.B * a.tiles_y * a.tiles_x;
-                a.wgs = r.sw.srd_wgs;
                 char kn[64];
                 const bool pipe16 = x.C == 16 && r.sw.srd_pipe;   // (opt-in: measured 6 % slower than srd_roll16, profiles/r06_srd_two_slice.txt)
                 if (pipe16) srd_pipe16_kernel_name(r.e->prec, with_pool, kn, sizeof kn);
@@ -285,10 +276,9 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
             char kn[64];
             snprintf(kn, sizeof kn, "dffw::srd_attention_kernel<%d, %d>", r.e->prec, feat.C);
             const double px = (double)feat.pixels();
-            r.prof_begin(kn, p + ".N_ch_attention", 2.0 * px * 4 * feat.C * feat.C, (with_pool ? 2.25 : 2.0) * px * feat.C * r.elem_bytes());
-            r.check(launch_srd_attention(r.e->prec, feat.p, out.p, i3->second.w32, i1->second.w32, feat.B, feat.N, feat.H, feat.W,
-                                         feat.C, with_pool ? pooled->p : nullptr, r.s), "srd_attention");
-            r.prof_end();
+            r.launch_unnamed(kn, p, ".N_ch_attention", 2.0 * px * 4 * feat.C * feat.C, (with_pool ? 2.25 : 2.0) * px * feat.C * r.elem_bytes(), "srd_attention", 0, [&](unsigned long long *) {
+                return launch_srd_attention(r.e->prec, feat.p, out.p, i3->second.w32, i1->second.w32, feat.B, feat.N, feat.H, feat.W, feat.C, with_pool ? pooled->p : nullptr, r.s);
+            });
         }
     } else if (feat.C == 32 && i3 != r.e->convs.end() && i1 != r.e->convs.end() && i3->second.watt && i1->second.watt && feat.W % 16 == 0 &&
                !r.sw.on(SW_NO_FUSED_ATTENTION)) {
@@ -297,10 +287,9 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
             char kn[64];
             snprintf(kn, sizeof kn, "dffw::srd_attention_mfma<%d>", r.e->prec);
             const double px = (double)feat.pixels();
-            r.prof_begin(kn, p + ".N_ch_attention", 2.0 * px * 4 * feat.C * feat.C, 2.0 * px * feat.C * r.elem_bytes());
-            r.check(launch_srd_attention_mfma(r.e->prec, feat.p, out.p, i3->second.watt, i1->second.watt, feat.B, feat.N, feat.H, feat.W, r.s),
-                    "srd_attention_mfma");
-            r.prof_end();
+            r.launch_unnamed(kn, p, ".N_ch_attention", 2.0 * px * 4 * feat.C * feat.C, 2.0 * px * feat.C * r.elem_bytes(), "srd_attention_mfma", 0, [&](unsigned long long *) {
+                return launch_srd_attention_mfma(r.e->prec, feat.p, out.p, i3->second.watt, i1->second.watt, feat.B, feat.N, feat.H, feat.W, r.s);
+            });
         }
     } else {
         ConvOpt o3; o3.relu = 1;
@@ -344,9 +333,8 @@ static Act efd(Run &r, const std::string &p, const Act &x, Act *pooled = nullptr
     if (fused(8, ty, tx) && ca->second.wroll8 && cb->second.wroll8) {
         Act out = r.act(x.B, x.N, Ho, Wo, 16);
         if (r.ok() && !r.dry) {
-            if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return out; }
             ConvArgs a = args(16, out.p);
-            a.zero = r.e->zero_page;
+            if (!(a.zero = r.zero_page())) return out;
             a.dbg = (r.sw.debug_flags & 6) | r.sw.path_bits();
             RollArgs t = roll_args(ca->second.wroll8, x.B, Ho / ty, Wo / tx, 1, r.sw.roll_wgs);
             t.wroll2 = cb->second.wroll8;
@@ -414,9 +402,8 @@ static Act pyramid(Run &r, const std::string &S, const Act &v3) {
         if (r.ok() && !r.dry) {
             char kn[48];
             snprintf(kn, sizeof kn, "dffw::pool3_kernel<%d>", r.e->prec);
-            r.prof_begin(kn, "avgpool (1,2,2)+(1,4,4)+(1,8,8)", 0.0, (double)(v3.pixels() + p8.pixels() + p16.pixels() + p32.pixels()) * v3.C * r.elem_bytes());
-            r.check(launch_pool3(r.e->prec, v3.p, p8.p, p16.p, p32.p, v3.B, v3.N, v3.H, v3.W, v3.C, r.s), "pool3");
-            r.prof_end();
+            r.launch_unnamed(kn, "avgpool (1,2,2)+(1,4,4)+(1,8,8)", "", 0.0, (double)(v3.pixels() + p8.pixels() + p16.pixels() + p32.pixels()) * v3.C * r.elem_bytes(), "pool3", 0,
+                             [&](unsigned long long *) { return launch_pool3(r.e->prec, v3.p, p8.p, p16.p, p32.p, v3.B, v3.N, v3.H, v3.W, v3.C, r.s); });
         }
     } else {
         p8 = r.pool(v3, 1, 2);
@@ -523,11 +510,9 @@ struct RegressQueue {
 static void regress(Run &r, RegressQueue &q, const char *tag, float *score, int B, int N, int h, int w, int H, int W, const float *fd,
                     const int64_t fst[4], float *out, bool merge) {
     if (!merge) {
-        if (r.ok() && !r.dry && out) {
-            r.prof_begin("dffw::regress_kernel", tag, 0.0, (double)B * N * h * w * 4.0 + (double)B * H * W * 4.0);
-            r.check(launch_regress(score, B, N, h, w, H, W, fd, fst[0], fst[1], fst[2], fst[3], out, r.s), tag);
-            r.prof_end();
-        }
+        if (r.ok() && !r.dry && out)
+            r.launch_unnamed("dffw::regress_kernel", tag, "", 0.0, (double)B * N * h * w * 4.0 + (double)B * H * W * 4.0, tag, 0,
+                             [&](unsigned long long *) { return launch_regress(score, B, N, h, w, H, W, fd, fst[0], fst[1], fst[2], fst[3], out, r.s); });
         r.drop_raw(score);
         return;
     }
@@ -547,9 +532,8 @@ static void flush_regress(Run &r, RegressQueue &q, int B, int N, int H, int W, c
         const bool fused = q.hd.n > 1 && N <= 16 && (int64_t)B * H * W < (1ll << 31) && !q.hd.nofuse;   // launch_regress_heads' own test
         // algorithmic bytes: the score volumes and depth maps + a dense focus-distance map once (the fused kernel does read it once; per-head launches re-read it)
         const double bytes = q.bytes + ((fst[2] || fst[3]) ? (double)B * N * H * W * 4.0 : 0.0);
-        r.prof_begin(fused ? "dffw::regress_fused_kernel" : "dffw::regress_kernel", "regress.mid_out+pred1+pred2+pred3", 0.0, bytes);
-        r.check(launch_regress_heads(q.hd, B, N, H, W, fd, fst[0], fst[1], fst[2], fst[3], r.s), "regress");
-        r.prof_end();
+        r.launch_unnamed(fused ? "dffw::regress_fused_kernel" : "dffw::regress_kernel", "regress.mid_out+pred1+pred2+pred3", "", 0.0, bytes, "regress", 0,
+                         [&](unsigned long long *) { return launch_regress_heads(q.hd, B, N, H, W, fd, fst[0], fst[1], fst[2], fst[3], r.s); });
     }
     for (int k = 0; k < q.nkeep; ++k) r.drop_raw(q.keep[k]);
     q.hd.n = 0;
@@ -558,8 +542,7 @@ static void flush_regress(Run &r, RegressQueue &q, int B, int N, int H, int W, c
 
 // raw != null: FS is not given; the stem reads the raw stack (or, when the tiled stem kernel does not serve this
 // shape, the stack is first expanded into a temporary fp32 volume from the workspace)
-static int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], int B, int N, int H, int W, float *const out[4],
-                     const RawStack *raw = nullptr) {
+int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], int B, int N, int H, int W, float *const out[4], const RawStack *raw) {
     const std::string P = "DFF_net";
     const int prec = r.e->prec;
     ConvOpt rl; rl.relu = 1;
@@ -606,9 +589,8 @@ static int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst
         if (r.ok() && !r.dry) {
             char kn[48];
             snprintf(kn, sizeof kn, "dffw::stack_in_kernel<%d>", prec);
-            r.prof_begin(kn, "stack_in", 0.0, (double)B * N * H * W * 3 * 4.0 + (double)B * N * H * (W + 2) * 8 * r.elem_bytes());
-            r.check(launch_stack_in(prec, FS, in.p, B, N, H, W, r.s), "stack_in");
-            r.prof_end();
+            r.launch_unnamed(kn, "stack_in", "", 0.0, (double)B * N * H * W * 3 * 4.0 + (double)B * N * H * (W + 2) * 8 * r.elem_bytes(), "stack_in", 0,
+                             [&](unsigned long long *) { return launch_stack_in(prec, FS, in.p, B, N, H, W, r.s); });
         }
         stem = r.conv(stem_name, in, rl);
         r.drop(in);
@@ -693,362 +675,6 @@ static int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst
     regress(r, rq, "regress.pred3", cost3, B, N, H, W, H, W, fd, fst, out[3], merge_heads);
     flush_regress(r, rq, B, N, H, W, fd, fst);
     return r.err;
-}
-
-// resnet_block_2d_OF (End_to_End.py:135-145): relu(feature(x) + BN(conv(relu(BN(conv_s(x))))))
-static Act of_block(Run &r, const std::string &p, const Act &x) {
-    ConvOpt rl; rl.relu = 1;
-    // stride-1 block with 16 output channels on whole 8 x 16 columns: conv.0, conv.2 and the shortcut in one streaming kernel
-    {
-        auto c0 = r.e->convs.find(p + ".conv.0.0"), c2 = r.e->convs.find(p + ".conv.2.0");
-        const auto end = r.e->convs.end();
-        const int co = (c0 != end) ? c0->second.def.cout : 0;
-        if (r.e->convs.find(p + ".feature") == end && c0 != end && c2 != end && c0->second.wsrd && c2->second.wsrd && (x.C == 8 || x.C == 16) &&
-            (co == 16 || (co == 8 && x.C == 8)) && c2->second.def.cout == co && c2->second.cin_all == co + x.C && x.H % 8 == 0 && x.W % 16 == 0 &&
-            (int64_t)x.B * (x.H / 8) * (x.W / 16) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_TILE)) {
-            Act out = r.act(x.B, x.N, x.H, x.W, co);
-            if (r.ok() && !r.dry) {
-                if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return out; }
-                SrdArgs a;
-                memset(&a, 0, sizeof a);
-                a.x = x.p; a.out = out.p;
-                a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd;
-                a.b0 = c0->second.bias; a.b2 = c2->second.bias;
-                a.zero = r.e->zero_page;
-                a.B = x.B; a.N = x.N; a.H = x.H; a.W = x.W;
-                a.tiles_y = x.H / 8; a.tiles_x = x.W / 16;
-                a.total_tiles = x.B * a.tiles_y * a.tiles_x;
-                a.wgs = r.sw.srd_wgs;
-                char kn[64];
-                if (co == 8) of_roll8_kernel_name(r.e->prec, kn, sizeof kn);
-                else of_roll_kernel_name(r.e->prec, x.C == 8, kn, sizeof kn);
-                g_last_kernel = kn;
-                const double px = (double)x.pixels();
-                const LayerDef &L0 = c0->second.def;
-                r.prof_begin(kn, p, 2.0 * px * (9.0 * L0.cin * co + 9.0 * co * co + (double)L0.cin * co), px * (x.C + co) * r.elem_bytes());
-                r.check(co == 8 ? launch_of_roll8(r.e->prec, a, r.s) : launch_of_roll(r.e->prec, x.C == 8, a, r.s), "of_roll");
-                r.prof_end();
-            }
-            return out;
-        }
-    }
-    {
-        // the 8 -> 16 down-sampling block on whole 8 x 16 output columns: one streaming kernel (of_s2_kernel, dffw_srd_roll.hip)
-        auto c0 = r.e->convs.find(p + ".conv.0.0"), c2 = r.e->convs.find(p + ".conv.2.0"), cf = r.e->convs.find(p + ".feature");
-        const auto end = r.e->convs.end();
-        if (c0 != end && c2 != end && cf != end && x.C == 8 && c0->second.wsrd && c2->second.wsrd && cf->second.wsrd && c0->second.def.sh == 2 &&
-            c0->second.def.cout == 16 && c2->second.def.cout == 16 && c2->second.cin_all == 16 && cf->second.def.sh == 2 && cf->second.def.cout == 16 &&
-            x.H % 16 == 0 && x.W % 32 == 0 && (int64_t)x.B * (x.H / 16) * (x.W / 32) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_TILE)) {
-            Act out = r.act(x.B, x.N, x.H / 2, x.W / 2, 16);
-            if (r.ok() && !r.dry) {
-                SrdArgs a;
-                memset(&a, 0, sizeof a);
-                a.x = x.p; a.out = out.p;
-                a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd; a.w3f = cf->second.wsrd;
-                a.b0 = c0->second.bias; a.b2 = c2->second.bias;
-                a.B = x.B; a.N = x.N; a.H = out.H; a.W = out.W;
-                a.tiles_y = out.H / 8; a.tiles_x = out.W / 16;
-                a.total_tiles = x.B * a.tiles_y * a.tiles_x;
-                a.wgs = r.sw.srd_wgs;
-                char kn[64];
-                of_s2_kernel_name(r.e->prec, kn, sizeof kn);
-                g_last_kernel = kn;
-                const double px = (double)out.pixels();
-                r.prof_begin(kn, p, 2.0 * px * (9.0 * 8 * 16 + 9.0 * 16 * 16 + 8.0 * 16), (4.0 * px * 8 + px * 16) * r.elem_bytes());
-                r.check(launch_of_s2(r.e->prec, a, r.s), "of_s2");
-                r.prof_end();
-            }
-            return out;
-        }
-    }
-    Act t = r.conv(p + ".conv.0.0", x, rl);
-    if (r.e->convs.find(p + ".feature") == r.e->convs.end()) {   // stride-1 block: shortcut folded into conv.2 over [t | x]
-        ConvOpt o; o.relu = 1; o.in1 = &x;
-        Act out = r.conv(p + ".conv.2.0", t, o);
-        r.drop(t);
-        return out;
-    }
-    Act f = r.conv(p + ".feature", x);
-    ConvOpt o; o.relu = 1; o.res0 = &f;
-    Act out = r.conv(p + ".conv.2.0", t, o);
-    r.drop(t);
-    r.drop(f);
-    return out;
-}
-
-// The first feature block (OF_feature.0, End_to_End.py:72) from the fp32 stack FS (B,3,N,H,W): of_first_kernel reads the stack itself
-// when its streaming form applies (of_roll8 with the record conversion inside its fill: the 8-channel record volume of the stack is
-// neither written nor read), else the stack is converted to an 8-channel record volume and of_block() takes it.
-static Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W) {
-    const int prec = r.e->prec;
-    Act a0;
-    auto c0 = r.e->convs.find(p0 + ".conv.0.0"), c2 = r.e->convs.find(p0 + ".conv.2.0");
-    const auto end = r.e->convs.end();
-    const bool first = c0 != end && c2 != end && r.e->convs.find(p0 + ".feature") == end && c0->second.wsrd && c2->second.wsrd &&
-                       c0->second.def.cin == 3 && c0->second.def.cout == 8 && c2->second.def.cout == 8 && c2->second.cin_all == 16 && H % 8 == 0 &&
-                       W % 16 == 0 && (int64_t)B * (H / 8) * (W / 16) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_OF_FIRST) &&
-                       !r.sw.on(SW_NO_TILE);
-    if (first) {
-        a0 = r.act(B, N, H, W, 8);
-        if (r.ok() && !r.dry) {
-            SrdArgs a;
-            memset(&a, 0, sizeof a);
-            a.w3 = FS; a.out = a0.p;
-            a.w0 = c0->second.wsrd; a.w2 = c2->second.wsrd;
-            a.b0 = c0->second.bias; a.b2 = c2->second.bias;
-            a.B = B; a.N = N; a.H = H; a.W = W;
-            a.tiles_y = H / 8; a.tiles_x = W / 16;
-            a.total_tiles = B * a.tiles_y * a.tiles_x;
-            a.wgs = r.sw.srd_wgs;
-            char kn[64];
-            of_first_kernel_name(prec, kn, sizeof kn);
-            g_last_kernel = kn;
-            const double px = (double)B * N * H * W;
-            r.prof_begin(kn, p0, 2.0 * px * (9.0 * 3 * 8 + 9.0 * 8 * 8 + 3.0 * 8), px * (3 * 4.0 + 8 * r.elem_bytes()));
-            r.check(launch_of_first(prec, a, r.s), "of_first");
-            r.prof_end();
-        }
-    } else {
-        Act in = r.act(B, N, H, W, 8);
-        if (r.ok() && !r.dry) {
-            char kn[56];
-            snprintf(kn, sizeof kn, "dffw::from_ncdhw_pad_kernel<%d>", prec);
-            r.prof_begin(kn, "flow.stack_in", 0.0, (double)B * N * H * W * (3 * 4.0 + 8 * r.elem_bytes()));
-            r.check(launch_from_ncdhw_pad(prec, FS, in.p, B, 3, 8, N, H, W, r.s), "from_ncdhw_pad");
-            r.prof_end();
-        }
-        a0 = of_block(r, p0, in);
-        r.drop(in);
-    }
-    return a0;
-}
-
-// End_to_End.Network.forward (End_to_End.py:13-16): FlowNetwork.forward (End_to_End.py:71-105) aligns the stack,
-// DFF_net runs on the aligned stack.  `aligned` receives the warped focal stack (the 5th return value).
-static int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W,
-                   float *const out[4], float *aligned) {
-    const std::string P = "optical_flow_aggregation";
-    const int prec = r.e->prec;
-    ConvOpt rl; rl.relu = 1;
-    // three feature levels: full, 1/2, 1/4 resolution                               End_to_End.py:72-74
-    Act a0 = of_first_block(r, P + ".OF_feature.0", FS, B, N, H, W);
-    Act fe1 = of_block(r, P + ".OF_feature.1", a0);
-    r.drop(a0);
-    r.tap("fe1", fe1);
-    Act a1 = of_block(r, P + ".OF_feature1.0", fe1);
-    Act fe2 = of_block(r, P + ".OF_feature1.1", a1);
-    r.drop(a1);
-    r.tap("fe2", fe2);
-    Act a2 = of_block(r, P + ".OF_feature2.0", fe2);
-    Act fe3 = of_block(r, P + ".OF_feature2.1", a2);
-    r.drop(a2);
-    r.tap("fe3", fe3);
-
-    const int64_t na = (int64_t)B * 3 * N;
-    float *alpha = (float *)r.raw(na * sizeof(float));   // accumulated (scale offset, x shift, y shift) per (b, slice)
-    float *rawh = (float *)r.raw(na * sizeof(float));    // last head output before damping (debug tap)
-    if (r.ok() && !r.dry) r.check(hipMemsetAsync(alpha, 0, na * sizeof(float), r.s), "alpha memset");
-
-    struct Level { Act *fe; const char *head; const char *tap; const char *atap; };
-    Level levels[3] = {{&fe3, ".conv1", "head3", "alpha3"}, {&fe2, ".conv2", "head2", "alpha2"}, {&fe1, ".conv3", "head1", nullptr}};
-    for (const Level &lv : levels) {                      // coarse to fine, End_to_End.py:77-103
-        Act &fe = *lv.fe;
-        const std::string hp = P + lv.head;
-        char kn[56];
-        snprintf(kn, sizeof kn, "dffw::flow_volume_kernel<%d>", prec);
-        Act y0;
-        if (r.e->convs.count(hp + ".0.0#ref") && !r.sw.on(SW_NO_HEAD_SPLIT)) {
-            // the head's first conv is linear in its input channels: the part over the warped reference slice is the same
-            // for all N slices of a sample, so it runs once per sample (1/N of the work, no ref channels in the volume) and
-            // enters the per-slice conv over [cur | flow] as a slice-broadcast residual in front of the ReLU
-            Act refw = r.act(B, 1, fe.H, fe.W, fe.C);
-            // [cur | flow] is not materialised when head_warp_kernel serves the level (8- and 16-channel levels, whole 8 x 16 columns): it
-            // samples the warped features while staging its tiles.  (The same inside conv_tile's fill was measured slower than
-            // flow_volume + LDS-DMA fill -- 1.64 vs 0.85 + 0.93 ms at level 1: a tile's gathers are one dependent latency chain per
-            // workgroup there -- and removed again.)
-            auto ccur = r.e->convs.find(hp + ".0.0#cur");
-            const bool roll = (fe.C == 8 || fe.C == 16) && ccur != r.e->convs.end() && ccur->second.wsrd && ccur->second.def.cin == fe.C + 2 &&
-                              ccur->second.def.cout == 2 * fe.C && fe.H % 8 == 0 &&
-                              fe.W % 16 == 0 && (int64_t)B * (fe.H / 8) * (fe.W / 16) >= r.sw.roll_min_units && (int64_t)B * N <= head_warp_max_planes() && !r.sw.on(SW_NO_HEAD_WARP) && !r.sw.on(SW_NO_TILE);
-            Act vol;
-            if (!roll) vol = r.act(B, N, fe.H, fe.W, fe.C + 8);
-            if (r.ok() && !r.dry) {
-                r.prof_begin(kn, std::string("flow") + lv.head + ".volume", 0.0,
-                             ((double)(roll ? 0 : fe.pixels()) * (2.0 * fe.C + 8) + (double)refw.pixels() * 2.0 * fe.C) * r.elem_bytes());
-                r.check(launch_flow_volume(prec, fe.p, refw.p, alpha, fov, B, N, fe.H, fe.W, fe.C, 2, r.s), "flow_volume ref");
-                if (!roll) r.check(launch_flow_volume(prec, fe.p, vol.p, alpha, fov, B, N, fe.H, fe.W, fe.C, 1, r.s), "flow_volume cur");
-                r.prof_end();
-            }
-            if (!roll) r.drop(fe);
-            // per-slice conv: the B reference slices are presented as the B slices of ONE sample so that the 5-slice tiles
-            // are filled (same memory either way)
-            Act refw1 = refw;
-            refw1.B = 1; refw1.N = B;
-            Act refpart = r.conv(hp + ".0.0#ref", refw1);
-            refpart.B = B; refpart.N = 1;
-            r.drop(refw);
-            if (roll) {
-                y0 = r.act(B, N, fe.H, fe.W, 2 * fe.C);
-                if (r.ok() && !r.dry) {
-                    HeadWarpArgs ha;
-                    memset(&ha, 0, sizeof ha);
-                    ha.fe = fe.p; ha.ref = refpart.p; ha.out = y0.p;
-                    ha.w = ccur->second.wsrd; ha.bias = ccur->second.bias;
-                    ha.alpha = alpha; ha.fov = fov;
-                    ha.B = B; ha.N = N; ha.H = fe.H; ha.W = fe.W;
-                    ha.tiles_y = fe.H / 8; ha.tiles_x = fe.W / 16;
-                    ha.total_tiles = B * ha.tiles_y * ha.tiles_x;
-                    ha.wgs = r.sw.srd_wgs;
-                    char knw[64];
-                    head_warp_kernel_name(prec, fe.C, knw, sizeof knw);
-                    g_last_kernel = knw;
-                    const double px = (double)fe.pixels();
-                    r.prof_begin(knw, hp + ".0.0#cur", 2.0 * px * 9.0 * (fe.C + 2) * 2 * fe.C, (px * 3 + (double)refpart.pixels() * 2) * fe.C * r.elem_bytes());
-                    r.check(launch_head_warp(prec, fe.C, ha, r.s), "head_warp");
-                    r.prof_end();
-                }
-                r.drop(fe);
-            } else {
-                ConvOpt oc = rl;
-                oc.res0 = &refpart;
-                oc.res_bcast = true;
-                y0 = r.conv(hp + ".0.0#cur", vol, oc);
-                r.drop(vol);
-            }
-            r.drop(refpart);
-        } else {
-            const int Cv = 2 * fe.C + 8;                  // 2C+2 channels of End_to_End.py:81-84, padded to a multiple of 8
-            Act vol = r.act(B, N, fe.H, fe.W, Cv);
-            if (r.ok() && !r.dry) {
-                r.prof_begin(kn, std::string("flow") + lv.head + ".volume", 0.0, (double)fe.pixels() * (2.0 * fe.C + Cv) * r.elem_bytes());
-                r.check(launch_flow_volume(prec, fe.p, vol.p, alpha, fov, B, N, fe.H, fe.W, fe.C, 0, r.s), "flow_volume");
-                r.prof_end();
-            }
-            r.drop(fe);
-            y0 = r.conv(hp + ".0.0", vol, rl);
-            r.drop(vol);
-        }
-        Act y2;
-        auto c6 = r.e->convs.find(hp + ".6");
-        const bool tail_sums = c6 != r.e->convs.end() && c6->second.whead && !r.sw.on(SW_NO_HEAD_SUMS);
-        bool tail_done = false;
-        {
-            // two 16 -> 16 per-slice convs in a row (level-1 head at full resolution): one streaming kernel, the intermediate in LDS
-            auto c2 = r.e->convs.find(hp + ".2.0"), c4 = r.e->convs.find(hp + ".4.0");
-            const auto end = r.e->convs.end();
-            if (y0.C == 16 && c2 != end && c4 != end && c2->second.wsrd && c4->second.wsrd && c2->second.def.cout == 16 && c4->second.def.cout == 16 &&
-                c2->second.cin_all == 16 && c4->second.cin_all == 16 && y0.H % 8 == 0 && y0.W % 16 == 0 &&
-                (int64_t)y0.B * (y0.H / 8) * (y0.W / 16) >= r.sw.roll_min_units && !r.sw.on(SW_NO_FUSED_OF) && !r.sw.on(SW_NO_TILE)) {
-                // ... and when the head's tail runs as plane sums, the pair's output is not stored either: the kernel leaves nine
-                // 16-channel vectors per (slice, column) and head_tail_finish_tiles does the rest
-                const bool sums = tail_sums && c6->second.def.cin == 16 && !r.sw.on(SW_NO_HEAD_SUMS_FUSED);
-                const int tiles_y = y0.H / 8, tiles_x = y0.W / 16;
-                float *tsum = nullptr;
-                double *seg = nullptr;
-                if (sums) {
-                    tsum = (float *)r.raw((int64_t)B * N * tiles_y * tiles_x * 18 * 16 * sizeof(float));
-                    seg = (double *)r.raw(head_tail_tiles_scratch_bytes(B, N, 16));
-                }
-                else y2 = r.act(y0.B, y0.N, y0.H, y0.W, 16);
-                if (r.ok() && !r.dry) {
-                    if (r.e->ensure_zero_page() != DFFW_OK) { r.err = DFFW_EHIP; return r.err; }
-                    SrdArgs a;
-                    memset(&a, 0, sizeof a);
-                    a.x = y0.p; a.out = sums ? (uint16_t *)tsum : y2.p;
-                    a.w0 = c2->second.wsrd; a.w2 = c4->second.wsrd;
-                    a.b0 = c2->second.bias; a.b2 = c4->second.bias;
-                    a.zero = r.e->zero_page;
-                    a.B = y0.B; a.N = y0.N; a.H = y0.H; a.W = y0.W;
-                    a.tiles_y = tiles_y; a.tiles_x = tiles_x;
-                    a.total_tiles = y0.B * a.tiles_y * a.tiles_x;
-                    a.wgs = r.sw.srd_wgs;
-                    char kn2[64];
-                    of_roll_kernel_name(prec, false, kn2, sizeof kn2, sums);
-                    g_last_kernel = kn2;
-                    const double px = (double)y0.pixels();
-                    r.prof_begin(kn2, hp + (sums ? ".2.0+.4.0+.6+mean" : ".2.0+.4.0"), 2.0 * px * (2 * 9.0 * 16 * 16 + (sums ? 9.0 * 16 * 3 : 0.0)),
-                                 px * (sums ? 16 : 32) * r.elem_bytes());
-                    r.check(launch_of_roll(prec, false, a, r.s, sums), "of_roll (head)");
-                    r.prof_end();
-                    if (sums) {
-                        r.prof_begin("dffw::head_tail_tiles_reduce_kernel", hp + ".6+mean (finish)", 0.0, (double)B * N * tiles_y * tiles_x * 18 * 16 * 4.0);
-                        r.check(launch_head_tail_tiles(tsum, seg, tiles_y, tiles_x, c6->second.whead, alpha, rawh, B, N, y0.H, y0.W, 16, r.s), "head_tail_tiles");
-                        r.prof_end();
-                    }
-                }
-                r.drop(y0);
-                if (sums) {
-                    r.drop_raw(seg);
-                    r.drop_raw(tsum);
-                    tail_done = true;
-                }
-            } else {
-                Act y1 = r.conv(hp + ".2.0", y0, rl);
-                r.drop(y0);
-                // the head's tail as plane sums and a row-sums kernel for the third conv: its output is not stored either
-                if (tail_sums && c6->second.def.cin == y1.C && c4 != end && c4->second.def.cout == y1.C && !r.sw.on(SW_NO_HEAD_SUMS_FUSED) &&
-                    r.sums_conv_ok(hp + ".4.0", y1.B, y1.N, y1.H, y1.W)) {
-                    const int tiles_x = y1.W / c4->second.tile.cfg->tx;
-                    float *rows = (float *)r.raw((int64_t)B * N * y1.H * tiles_x * 3 * y1.C * sizeof(float));
-                    double *seg = (double *)r.raw(head_tail_tiles_scratch_bytes(B, N, y1.C));
-                    ConvOpt os = rl;
-                    os.sums = rows;
-                    r.conv(hp + ".4.0", y1, os);
-                    if (r.ok() && !r.dry) {
-                        r.prof_begin("dffw::head_tail_rows_reduce_kernel", hp + ".6+mean (finish)", 0.0, (double)B * N * y1.H * tiles_x * 3 * y1.C * 4.0);
-                        r.check(launch_head_tail_rows(rows, seg, tiles_x, c6->second.whead, alpha, rawh, B, N, y1.H, y1.W, y1.C, r.s), "head_tail_rows");
-                        r.prof_end();
-                    }
-                    r.drop_raw(seg);
-                    r.drop_raw(rows);
-                    tail_done = true;
-                } else {
-                    y2 = r.conv(hp + ".4.0", y1, rl);
-                }
-                r.drop(y1);
-            }
-        }
-        const int64_t hw = (int64_t)fe.H * fe.W;
-        if (tail_done) {
-        } else if (tail_sums && c6->second.def.cin == y2.C) {
-            // last conv + plane mean collapsed into plane sums of y2 (dffw_kernels.hip, "alpha head tail"): y2 is read once, the
-            // 3-plane fp32 head output is never formed
-            const int nchunk = head_tail_chunks(B, N, hw);
-            double *partial = (double *)r.raw((int64_t)B * N * (nchunk + 4) * y2.C * sizeof(double));
-            if (r.ok() && !r.dry) {
-                char kn6[64];
-                snprintf(kn6, sizeof kn6, "dffw::plane_sums_kernel<%d>", prec);
-                r.prof_begin(kn6, hp + ".6+mean", 2.0 * (double)y2.pixels() * 9.0 * y2.C * 3, (double)y2.pixels() * y2.C * r.elem_bytes());
-                r.check(launch_head_tail(prec, y2.p, partial, c6->second.whead, alpha, rawh, B, N, y2.H, y2.W, y2.C, r.s), "head_tail");
-                r.prof_end();
-            }
-            r.drop_raw(partial);
-            r.drop(y2);
-        } else {
-            float *hf = (float *)r.raw(na * hw * sizeof(float));
-            ConvOpt of; of.outf = hf; of.outf_ch = 3;
-            r.conv(hp + ".6", y2, of);
-            r.drop(y2);
-            if (r.ok() && !r.dry) {
-                r.prof_begin("dffw::alpha_mean_kernel", std::string("flow") + lv.head + ".mean", 0.0, (double)na * hw * 4.0);
-                r.check(launch_alpha_mean(hf, alpha, rawh, B, N, hw, r.s), "alpha_mean");
-                r.prof_end();
-            }
-            r.drop_raw(hf);
-        }
-        r.tap_f32(lv.tap, rawh, na);
-        if (lv.atap) r.tap_f32(lv.atap, alpha, na);   // (after level 1 it is the final "alpha" below)
-    }
-    r.tap_f32("alpha", alpha, na);
-    if (r.ok() && !r.dry) {                               // End_to_End.py:104
-        r.prof_begin("dffw::fov_warp_kernel", "flow.warp_stack", 0.0, (double)B * N * H * W * 3 * 8.0);
-        r.check(launch_fov_warp(FS, alpha, fov, aligned, nullptr, B, 3, N, H, W, 0, r.s), "fov_warp");
-        r.prof_end();
-    }
-    r.drop_raw(rawh);
-    r.drop_raw(alpha);
-    if (!r.ok()) return r.err;
-    return run_depth(r, aligned, fd, fst, B, N, H, W, out);
 }
 
 static int check_dims(int B, int N, int H, int W) {

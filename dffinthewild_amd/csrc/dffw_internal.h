@@ -1,4 +1,4 @@
-// Internal declarations shared by the graph executor (dffw_engine.cpp) and the gfx950 kernels.
+// Internal declarations shared by the graph executors (dffw_engine.cpp, dffw_align.cpp) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

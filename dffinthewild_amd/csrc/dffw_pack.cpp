@@ -6,6 +6,7 @@
 
 #include "../../include/dffw.h"
 #include "dffw_conv_roll.h"
+#include "dffw_align.h"
 #include "dffw_srd_roll.h"
 #include "dffw_pack.h"
 

@@ -1,5 +1,6 @@
 // Private to the host side of libdffw.so: the workspace arena, the engine object, the DFFW_* switch snapshot and the per-forward
-// executor state (Run) that the graphs of dffw_engine.cpp and the conv dispatch of dffw_dispatch.cpp share.  No kernel includes this.
+// executor state (Run) that the graphs of dffw_engine.cpp (depth network, C ABI) and dffw_align.cpp (alignment network) and the conv
+// dispatch of dffw_dispatch.cpp share.  No kernel includes this.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dffw.h"
+#include "dffw_align.h"
 #include "dffw_conv_roll.h"
 #include "dffw_conv_tile.h"
 #include "dffw_internal.h"
@@ -306,6 +308,35 @@ inline RollArgs roll_args(const uint16_t *filter, int B, int tiles_y, int tiles_
     return t;
 }
 
+// the SrdArgs of one launch of a fused block kernel over columns of ty x tx pixels of a (B,N,H,W) grid: c0 / c2 are the block's two 1x3x3
+// convs; the caller adds what only its kernel reads (pooled, the attention weights, the shortcut, zero).  of_first has no record volume:
+// its `x` is null and the caller puts the planar fp32 focal stack into a.w3, which no alignment kernel uses for weights
+inline SrdArgs srd_args(const uint16_t *x, uint16_t *out, const PackedConv &c0, const PackedConv &c2, int B, int N, int H, int W, int ty, int tx, int wgs) {
+    SrdArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = x; a.out = out;
+    a.w0 = c0.wsrd; a.w2 = c2.wsrd;
+    a.b0 = c0.bias; a.b2 = c2.bias;
+    a.B = B; a.N = N; a.H = H; a.W = W;
+    a.tiles_y = H / ty; a.tiles_x = W / tx;
+    a.total_tiles = B * a.tiles_y * a.tiles_x;
+    a.wgs = wgs;
+    return a;
+}
+// ... and the HeadWarpArgs of head_warp over the 8 x 16 columns of the level features `fe`: `ref` the per-sample reference part, `cur` the [cur | flow] filter
+inline HeadWarpArgs head_warp_args(const Act &fe, const uint16_t *ref, uint16_t *out, const PackedConv &cur, const float *alpha, const float *fov, int wgs) {
+    HeadWarpArgs a;
+    memset(&a, 0, sizeof a);
+    a.fe = fe.p; a.ref = ref; a.out = out;
+    a.w = cur.wsrd; a.bias = cur.bias;
+    a.alpha = alpha; a.fov = fov;
+    a.B = fe.B; a.N = fe.N; a.H = fe.H; a.W = fe.W;
+    a.tiles_y = fe.H / 8; a.tiles_x = fe.W / 16;
+    a.total_tiles = fe.B * a.tiles_y * a.tiles_x;
+    a.wgs = wgs;
+    return a;
+}
+
 struct Run {
     dffw_engine *e;
     hipStream_t s;
@@ -419,15 +450,30 @@ struct Run {
         check(hipEventRecord(e->recs.back().e1, s), "hipEventRecord");
     }
     double elem_bytes() const { return 2.0 * prec_parts(e->prec); }
-    // the shell of one kernel launch: the name dffw_last_conv_kernel() reports, the profile record, `go` (the launcher call), the record's end.
+    // the shell of one kernel launch: the profile record, `go` (the launcher call; two launches that share a record go into one `go`), the record's end.
     // `trace_words` > 0: the launch of a layer named by DFFW_TRACE_LAYER also gets a zeroed timeline of that many u64, handed to go(); the caller's trace_end() writes it out
     template <class Go>
-    void launch(const char *kernel, const std::string &layer, const char *suffix, double flops, double bytes, const char *what, size_t trace_words, Go &&go) {
-        dffw_set_last_conv_kernel(kernel);
+    void launch_unnamed(const char *kernel, const std::string &layer, const char *suffix, double flops, double bytes, const char *what, size_t trace_words, Go &&go) {
         prof_begin(kernel, layer, flops, bytes, suffix);
         unsigned long long *trace = trace_words ? trace_begin(layer, trace_words) : nullptr;
         check(go(trace), what);
         prof_end();
+    }
+    // ... of a conv or fused-block kernel: dffw_last_conv_kernel() then reports `kernel` (the data movers, reductions and pools go through launch_unnamed)
+    template <class Go>
+    void launch(const char *kernel, const std::string &layer, const char *suffix, double flops, double bytes, const char *what, size_t trace_words, Go &&go) {
+        dffw_set_last_conv_kernel(kernel);
+        launch_unnamed(kernel, layer, suffix, flops, bytes, what, trace_words, go);
+    }
+    // the engine's page of zeros (what out-of-volume LDS-DMA lanes read), made at first use; null with `err` set when that fails
+    const uint16_t *zero_page() {
+        if (e->ensure_zero_page() != DFFW_OK) err = DFFW_EHIP;
+        return ok() ? e->zero_page : nullptr;
+    }
+    // the packed layer `name`, or null
+    const PackedConv *layer(const std::string &name) const {
+        auto it = e->convs.find(name);
+        return it == e->convs.end() ? nullptr : &it->second;
     }
 
     // step timeline of a persistent streaming kernel (library built with `make TRACE=1`; DFFW_TRACE_LAYER=<layer> DFFW_TRACE_OUT=<file>):
@@ -459,12 +505,12 @@ struct Run {
 
     // does the LDS-tiled kernel serve layer `name` for an output grid of gH x gW (same test as in conv())?
     bool tiled(const std::string &name, int gH, int gW) const {
-        auto it = e->convs.find(name);
-        return it != e->convs.end() && conv_tiled(it->second, sw, gH, gW);
+        const PackedConv *pc = layer(name);
+        return pc && conv_tiled(*pc, sw, gH, gW);
     }
     bool sums_conv_ok(const std::string &name, int B, int N, int H, int W) const {
-        auto it = e->convs.find(name);
-        return it != e->convs.end() && conv_sums_ok(it->second, sw, B, N, H, W);
+        const PackedConv *pc = layer(name);
+        return pc && conv_sums_ok(*pc, sw, B, N, H, W);
     }
 
     Act conv(const std::string &name, const Act &in0, const ConvOpt &o = ConvOpt());   // dffw_dispatch.cpp
@@ -474,9 +520,8 @@ struct Run {
         if (ok() && !dry) {
             char kn[48];
             snprintf(kn, sizeof kn, "dffw::pool_kernel<%d>", e->prec);
-            prof_begin(kn, mode == 0 ? "maxpool" : "avgpool", 0.0, (double)(x.pixels() + out.pixels()) * x.C * elem_bytes());
-            check(launch_pool(e->prec, mode, k, x.p, out.p, x.B, x.N, x.H, x.W, x.C, s), "pool");
-            prof_end();
+            launch_unnamed(kn, mode == 0 ? "maxpool" : "avgpool", "", 0.0, (double)(x.pixels() + out.pixels()) * x.C * elem_bytes(), "pool", 0,
+                           [&](unsigned long long *) { return launch_pool(e->prec, mode, k, x.p, out.p, x.B, x.N, x.H, x.W, x.C, s); });
         }
         return out;
     }
@@ -505,5 +550,11 @@ struct Run {
             }
     }
 };
+
+// the graphs: the depth network (dffw_engine.cpp) and, in front of it, the alignment network of End_to_End (dffw_align.cpp)
+int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], int B, int N, int H, int W, float *const out[4], const RawStack *raw = nullptr);
+int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W, float *const out[4], float *aligned);
+Act of_block(Run &r, const std::string &p, const Act &x);
+Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W);
 
 }  // namespace dffw

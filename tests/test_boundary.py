@@ -179,8 +179,9 @@ def test_isa_wait_lint_finds_the_round6_hazard_and_nothing_else():
     assert clean.returncode == 0, clean.stdout
     bad = subprocess.run([sys.executable, tool, src], capture_output=True, text=True, env=dict(os.environ, LINT_DEFS="-DDFFW_SLICE_HAZARD=2"))
     assert bad.returncode == 1 and "conv_slice64_head" in bad.stdout, bad.stdout
-    # the alignment network's streaming kernels (every of_* and head_warp kernel) and the fused SRD kernels: no hazard either
-    # (ASSUMED entries, where the lint takes a wait's coverage on trust, are printed, not failed)
-    roll = subprocess.run([sys.executable, tool, os.path.join(root, "dffinthewild_amd", "csrc", "dffw_srd_roll.hip")], capture_output=True, text=True)
-    print(roll.stdout)
-    assert roll.returncode == 0 and "HAZARD" not in roll.stdout and "dffw_srd_roll.hip" in roll.stdout, roll.stdout
+    # the alignment network's streaming kernels (every of_* and head_warp kernel, dffw_align.hip) and the fused SRD kernels (dffw_srd_roll.hip): no
+    # hazard either (ASSUMED entries, where the lint takes a wait's coverage on trust, are printed, not failed)
+    for name in ("dffw_srd_roll.hip", "dffw_align.hip"):
+        roll = subprocess.run([sys.executable, tool, os.path.join(root, "dffinthewild_amd", "csrc", name)], capture_output=True, text=True)
+        print(roll.stdout)
+        assert roll.returncode == 0 and "HAZARD" not in roll.stdout and name in roll.stdout, roll.stdout

@@ -271,7 +271,7 @@ def _profiled_kernels(model, *inputs):
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16", "bf16"])
 @pytest.mark.parametrize("B,H,W", [(1, 256, 256), (3, 96, 224), (4, 256, 256)])
 def test_hip_e2e_head_warp_streaming_kernel(lib_built, monkeypatch, B, H, W, precision):
-    """head_warp_kernel (dffw_srd_roll.hip): the level-1 (8-channel, full resolution) and, on large enough batches, level-2 (16-channel,
+    """head_warp_kernel (dffw_align.hip): the level-1 (8-channel, full resolution) and, on large enough batches, level-2 (16-channel,
     half resolution) heads' first conv over [warp(fe) | flow] with the bilinear gather done one slice ahead while staging
     (End_to_End.py:88-101 without the warped volume) against flow_volume + conv_tile (DFFW_NO_HEAD_WARP):
     magnifying, shrinking and out-of-image warps, columns on every image border; the profile proves which kernel ran; default
@@ -378,7 +378,7 @@ def test_hip_e2e_head_tail_as_plane_sums(lib_built, monkeypatch, B, H, W, precis
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16", "bf16"])
 @pytest.mark.parametrize("B,H,W", [(1, 256, 256), (2, 128, 256), (4, 256, 256), (9, 96, 160)])
 def test_hip_e2e_fused_alignment_blocks_match_two_launch_form(lib_built, monkeypatch, B, H, W, precision):
-    """of_roll8 / of_roll (dffw_srd_roll.hip): the stride-1 residual blocks of the alignment network (End_to_End.py:135-145:
+    """of_roll8 / of_roll (dffw_align.hip): the stride-1 residual blocks of the alignment network (End_to_End.py:135-145:
     OF_feature.0, OF_feature.1 at full resolution, OF_feature1.1 at half) as one streaming kernel each (conv.0 -> t in LDS ->
     conv.2 + 1x1x1 shortcut), against the two-launch form on shapes large enough for whole-column grids, and against the oracle."""
     g, sd, FS, fd, fov = load(SMOOTH[0])

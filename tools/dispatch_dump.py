@@ -1,5 +1,6 @@
 """What the conv dispatch decides, case by case: one line per kernel launch of one profiled forward (kernel name, layer label, flops, bytes,
-in launch order, from Engine.profile_collect()), then dffw_workspace_bytes, then the sha256 of every output tensor.  Weights and inputs are seeded,
+in launch order, from Engine.profile_collect()), then dffw_workspace_bytes, then the sha256 of every output tensor (a shape the library refuses
+shows as one `rejected` line with its message).  Weights and inputs are seeded,
 and only the public engine API is used, so two builds of the library (DFFW_LIB_PATH) are compared with `diff`.
 
 The lines hold what the roofline table and the kernel-name assertions see; the grid of a launch (zsplit, persistent workgroups, output-tile offset) is not in
@@ -28,6 +29,14 @@ SWITCH_SETS = [{"DFFW_" + n: "1"} for n in (
     "NO_NARROW", "NO_SMALL", "NO_STEM_PAIR", "NO_STEM_PIPE", "NO_FUSED_EFD", "NO_FUSED_SRD", "NO_LEAN_TILE", "NO_LEAN_ROLL")] + [
     {"DFFW_ROLL_MIN_UNITS": "1"}, {"DFFW_ROLL_MIN_UNITS": "1000000"}, {"DFFW_ROLL_MIN_UNITS": "1000000", "DFFW_NO_ROLLT": "1"},
     {"DFFW_ROLLK_MERGE_BELOW": "1"}, {"DFFW_ROLL_ZSPLIT": "2"}, {"DFFW_ROLL_WGS": "8"}, {"DFFW_SMALL_MAX_UNITS": "256"}, {"DFFW_KSPLIT_TARGET": "256"}]
+# ... and the ones that walk every form the alignment network chooses between (of_block(), of_first_block(), align_level() in dffw_align.cpp)
+E2E_SWITCH_SETS = [{"DFFW_" + n: "1"} for n in (
+    "NO_HEAD_SPLIT", "NO_HEAD_WARP", "NO_HEAD_SUMS", "NO_HEAD_SUMS_FUSED", "NO_FUSED_OF", "NO_OF_FIRST", "NO_TILE", "NO_SLICE32")] + [
+    {"DFFW_ROLL_MIN_UNITS": "1"}, {"DFFW_ROLL_MIN_UNITS": "1000000"}]
+
+
+def _tag(env):
+    return "+".join(k[5:] + ("" if k[5:8] == "NO_" else "=" + v) for k, v in env.items())
 
 
 def _cases():
@@ -47,9 +56,15 @@ def _cases():
         for b in (1, 8):
             out.append(("depth-%dx10x256x256-%s" % (b, prec), "depth", prec, (b, 10, 256, 256), {}))
     for env in SWITCH_SETS:
-        tag = "+".join(k[5:] + ("" if k[5:8] == "NO_" else "=" + v) for k, v in env.items())
         for b in (1, 8):
-            out.append(("depth-%dx10x256x256-%s" % (b, tag), "depth", "bf16x3", (b, 10, 256, 256), env))
+            out.append(("depth-%dx10x256x256-%s" % (b, _tag(env)), "depth", "bf16x3", (b, 10, 256, 256), env))
+    # End_to_End: 33 x 10 planes are more than head_warp keeps (320) on 1584 columns, so the split head runs over a [cur | flow] volume; 96 x 160 misses every
+    # streaming form (120 columns), once with 3 slices -- which the library rejects: the alignment heads are built for 10 -- and once with 10
+    for shp in [(33, 10, 64, 96), (1, 3, 96, 160), (1, 10, 96, 160)]:
+        out.append(("e2e-%dx%dx%dx%d" % shp, "e2e", "bf16x3", shp, {}))
+    for env in E2E_SWITCH_SETS:
+        for b in (1, 8):
+            out.append(("e2e-%dx10x480x640-%s" % (b, _tag(env)), "e2e", "bf16x3", (b, 10, 480, 640), env))
     return out
 
 
@@ -83,7 +98,14 @@ def _environment(env):
 
 
 def run_case(case):
-    """-> (launch lines, workspace bytes, [sha256 of each output])"""
+    """-> (launch lines, workspace bytes, [sha256 of each output]); a shape the library refuses: (one line with its message, -1, [])"""
+    try:
+        return _run_case(case)
+    except ValueError as e:   # (DFFW_EINVAL)
+        return ["rejected\t%s" % e], -1, []
+
+
+def _run_case(case):
     _, net, prec, (B, N, H, W), env = case
     eng = _engine(net, prec)
     dev = eng.device

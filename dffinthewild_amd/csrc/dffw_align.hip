@@ -12,8 +12,11 @@
 
 #include "dffw_align.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
+
+using SrdRow = KernelRow<SrdArgs>;   // dffw_persist.h
 
 // ---- of_roll8: the 8-channel stride-1 residual blocks of the alignment network (`OF_feature.0`, `OF_feature.1`, full resolution) --
 // As of_roll_kernel, in srd_roll_kernel's pixel-pair form (8 output channels): stage A = conv.0 -> t in LDS, stage B = conv.2 over
@@ -47,14 +50,8 @@ __global__ __launch_bounds__(256) void of_roll8_kernel(const SrdArgs a) {
     };
 
     // ---- columns of this workgroup: as conv_roll (XCD-contiguous ranges, round-robin inside the XCD) ----------------
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -265,14 +262,8 @@ __global__ __launch_bounds__(256) void of_first_kernel(const SrdArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -416,19 +407,10 @@ __global__ __launch_bounds__(256) void of_first_kernel(const SrdArgs a) {
     }
 }
 
-void of_first_kernel_name(int prec, char *buf, int n) { snprintf(buf, n, "dffw::of_first_kernel<%d>", prec); }
-
+static const SrdRow kOfFirst[] = {DFFW_ROW(256, of_first_kernel, 0), DFFW_ROW(256, of_first_kernel, 1), DFFW_ROW(256, of_first_kernel, 2)};   // [prec]
+void of_first_kernel_name(int prec, char *buf, int n) { copy_row_name(prec_row(kOfFirst, prec, 1, 0), buf, n); }
 hipError_t launch_of_first(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 1024;
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    switch (prec) {
-        case P_BF16X3: hipLaunchKernelGGL((of_first_kernel<P_BF16X3>), grid, block, 0, s, a); break;
-        case P_FP16: hipLaunchKernelGGL((of_first_kernel<P_FP16>), grid, block, 0, s, a); break;
-        case P_BF16: hipLaunchKernelGGL((of_first_kernel<P_BF16>), grid, block, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_row(prec_row(kOfFirst, prec, 1, 0), a.total_tiles, a.wgs > 0 ? a.wgs : 1024, 1, s, a);
 }
 
 // one operand fragment (hi [+ lo] plane) of an of_roll tile, and the counted wait that releases it (DS operations retire in order: `left` =
@@ -499,14 +481,8 @@ __global__ __launch_bounds__(256) void of_roll_kernel(const SrdArgs a) {
         asm volatile("ds_write_b64 %0, %1" ::"v"(lds0 + byte_off), "v"(d) : "memory");
     };
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -769,14 +745,8 @@ __global__ __launch_bounds__(CF == 8 ? 256 : 512) __attribute__((amdgpu_waves_pe
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -959,27 +929,15 @@ __global__ __launch_bounds__(CF == 8 ? 256 : 512) __attribute__((amdgpu_waves_pe
     }
 }
 
-void head_warp_kernel_name(int prec, int cf, char *buf, int n) { snprintf(buf, n, "dffw::head_warp_kernel<%d, %d>", prec, cf); }
-
+static const KernelRow<HeadWarpArgs> kHeadWarp[] = {   // [prec][cf 8 | 16]
+    DFFW_ROW(256, head_warp_kernel, 0, 8), DFFW_ROW(512, head_warp_kernel, 0, 16), DFFW_ROW(256, head_warp_kernel, 1, 8),
+    DFFW_ROW(512, head_warp_kernel, 1, 16), DFFW_ROW(256, head_warp_kernel, 2, 8), DFFW_ROW(512, head_warp_kernel, 2, 16),
+};
+static const KernelRow<HeadWarpArgs> *select_head_warp(int prec, int cf) { return cf == 8 || cf == 16 ? prec_row(kHeadWarp, prec, 2, cf == 16) : nullptr; }
+void head_warp_kernel_name(int prec, int cf, char *buf, int n) { copy_row_name(select_head_warp(prec, cf), buf, n); }
 hipError_t launch_head_warp(int prec, int cf, const HeadWarpArgs &a, hipStream_t s) {
     if ((int64_t)a.B * a.N > head_warp_max_planes()) return hipErrorInvalidValue;
-    const int want = a.wgs > 0 ? a.wgs : (cf == 8 ? 1024 : 512);
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8))));
-#define DFFW_HW_LAUNCH(P)                                                                             \
-    do {                                                                                              \
-        if (cf == 8) hipLaunchKernelGGL((head_warp_kernel<P, 8>), grid, dim3(256), 0, s, a);          \
-        else if (cf == 16) hipLaunchKernelGGL((head_warp_kernel<P, 16>), grid, dim3(512), 0, s, a);   \
-        else return hipErrorInvalidValue;                                                             \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3: DFFW_HW_LAUNCH(P_BF16X3); break;
-        case P_FP16: DFFW_HW_LAUNCH(P_FP16); break;
-        case P_BF16: DFFW_HW_LAUNCH(P_BF16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_HW_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_head_warp(prec, cf), a.total_tiles, a.wgs > 0 ? a.wgs : (cf == 8 ? 1024 : 512), 1, s, a);
 }
 
 // ---- of_s2: the down-sampling residual block of the alignment network at 8 -> 16 channels (End_to_End.py:135-145 with stride 2,
@@ -1009,14 +967,8 @@ __global__ __launch_bounds__(256) void of_s2_kernel(const SrdArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -1187,60 +1139,24 @@ __global__ __launch_bounds__(256) void of_s2_kernel(const SrdArgs a) {
     }
 }
 
-void of_s2_kernel_name(int prec, char *buf, int n) { snprintf(buf, n, "dffw::of_s2_kernel<%d>", prec); }
+static const SrdRow kOfS2[] = {DFFW_ROW(256, of_s2_kernel, 0), DFFW_ROW(256, of_s2_kernel, 1), DFFW_ROW(256, of_s2_kernel, 2)};   // [prec]
+void of_s2_kernel_name(int prec, char *buf, int n) { copy_row_name(prec_row(kOfS2, prec, 1, 0), buf, n); }
+hipError_t launch_of_s2(int prec, const SrdArgs &a, hipStream_t s) { return launch_row(prec_row(kOfS2, prec, 1, 0), a.total_tiles, a.wgs > 0 ? a.wgs : 512, 1, s, a); }
 
-hipError_t launch_of_s2(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 512;
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    switch (prec) {
-        case P_BF16X3: hipLaunchKernelGGL((of_s2_kernel<P_BF16X3>), grid, block, 0, s, a); break;
-        case P_FP16: hipLaunchKernelGGL((of_s2_kernel<P_FP16>), grid, block, 0, s, a); break;
-        case P_BF16: hipLaunchKernelGGL((of_s2_kernel<P_BF16>), grid, block, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
+static const SrdRow kOfRoll8[] = {DFFW_ROW(256, of_roll8_kernel, 0), DFFW_ROW(256, of_roll8_kernel, 1), DFFW_ROW(256, of_roll8_kernel, 2)};   // [prec]
+void of_roll8_kernel_name(int prec, char *buf, int n) { copy_row_name(prec_row(kOfRoll8, prec, 1, 0), buf, n); }
+hipError_t launch_of_roll8(int prec, const SrdArgs &a, hipStream_t s) { return launch_row(prec_row(kOfRoll8, prec, 1, 0), a.total_tiles, a.wgs > 0 ? a.wgs : 768, 1, s, a); }
 
-void of_roll8_kernel_name(int prec, char *buf, int n) { snprintf(buf, n, "dffw::of_roll8_kernel<%d>", prec); }
-
-hipError_t launch_of_roll8(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 768;
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    switch (prec) {
-        case P_BF16X3: hipLaunchKernelGGL((of_roll8_kernel<P_BF16X3>), grid, block, 0, s, a); break;
-        case P_FP16: hipLaunchKernelGGL((of_roll8_kernel<P_FP16>), grid, block, 0, s, a); break;
-        case P_BF16: hipLaunchKernelGGL((of_roll8_kernel<P_BF16>), grid, block, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-void of_roll_kernel_name(int prec, bool cin8, char *buf, int n, bool sums) {
-    if (sums) snprintf(buf, n, "dffw::of_roll_kernel<%d, %s, true>", prec, cin8 ? "true" : "false");
-    else snprintf(buf, n, "dffw::of_roll_kernel<%d, %s>", prec, cin8 ? "true" : "false");
-}
-
+static const SrdRow kOfRoll[] = {   // [prec][16 input channels | 8 | 16 with sums]
+    // the first two of a precision: labels, not the symbols (which end in the defaulted ", false"): the spelling the tests and the profile tools were recorded with
+    {"dffw::of_roll_kernel<0, false>", of_roll_kernel<0, false>, 256}, {"dffw::of_roll_kernel<0, true>", of_roll_kernel<0, true>, 256}, DFFW_ROW(256, of_roll_kernel, 0, false, true),
+    {"dffw::of_roll_kernel<1, false>", of_roll_kernel<1, false>, 256}, {"dffw::of_roll_kernel<1, true>", of_roll_kernel<1, true>, 256}, DFFW_ROW(256, of_roll_kernel, 1, false, true),
+    {"dffw::of_roll_kernel<2, false>", of_roll_kernel<2, false>, 256}, {"dffw::of_roll_kernel<2, true>", of_roll_kernel<2, true>, 256}, DFFW_ROW(256, of_roll_kernel, 2, false, true),
+};
+static const SrdRow *select_of_roll(int prec, bool cin8, bool sums) { return sums && cin8 ? nullptr : prec_row(kOfRoll, prec, 3, sums ? 2 : cin8); }
+void of_roll_kernel_name(int prec, bool cin8, char *buf, int n, bool sums) { copy_row_name(select_of_roll(prec, cin8, sums), buf, n); }
 hipError_t launch_of_roll(int prec, bool cin8, const SrdArgs &a, hipStream_t s, bool sums) {
-    const int want = a.wgs > 0 ? a.wgs : (cin8 ? 768 : 512);
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    if (sums && cin8) return hipErrorInvalidValue;
-#define DFFW_OF_LAUNCH(P)                                                                   \
-    do {                                                                                    \
-        if (sums) hipLaunchKernelGGL((of_roll_kernel<P, false, true>), grid, block, 0, s, a); \
-        else if (cin8) hipLaunchKernelGGL((of_roll_kernel<P, true>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((of_roll_kernel<P, false>), grid, block, 0, s, a);          \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3: DFFW_OF_LAUNCH(P_BF16X3); break;
-        case P_FP16: DFFW_OF_LAUNCH(P_FP16); break;
-        case P_BF16: DFFW_OF_LAUNCH(P_BF16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_OF_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_of_roll(prec, cin8, sums), a.total_tiles, a.wgs > 0 ? a.wgs : (cin8 ? 768 : 512), 1, s, a);
 }
 
 }  // namespace dffw

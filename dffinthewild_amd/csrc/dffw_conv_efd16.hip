@@ -23,6 +23,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -47,6 +48,7 @@ __device__ __forceinline__ void efd16_body(const ConvArgs &a, const RollArgs &t,
     const int g = lane >> 4, r = lane & 15;
     const int nt = (wave >> 1) & 1, ph = wave >> 2;   // this wave's 16-channel output tile and pixel half (operand tiles 2 ph, 2 ph + 1)
 
+    // (inline copy of persistent_range(), dffw_persist.h: through the helper hipcc allocates this kernel's registers differently)
     const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
     int ufirst, uend;
     {
@@ -301,14 +303,10 @@ bool efd16_ok(int prec, const ConvArgs &a, const RollArgs &t) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * 64 < (1ll << 31) && (int64_t)a.Ho * a.Wo * 128 < (1ll << 31);
 }
 
+static const RollRow kEfd16 = {"dffw::conv_efd16", conv_efd16, efd16::NW * 64};   // (no template arguments: the name is the symbol)
 hipError_t launch_conv_efd16(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 256;   // one 8-wave workgroup per CU
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(efd16::NW * 64);
-    hipLaunchKernelGGL(conv_efd16, grid, block, 0, s, a, t);
-    return hipGetLastError();
+    return launch_row(&kEfd16, t.total_tiles, t.wgs > 0 ? t.wgs : 256, 1, s, a, t);   // 256: one 8-wave workgroup per CU
 }
-
-void conv_efd16_kernel_name(char *buf, int n) { snprintf(buf, n, "dffw::conv_efd16"); }
+void conv_efd16_kernel_name(char *buf, int n) { copy_row_name(&kEfd16, buf, n); }
 
 }  // namespace dffw

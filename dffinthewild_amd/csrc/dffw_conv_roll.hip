@@ -21,6 +21,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -61,32 +62,11 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
     // units are numbered x fastest, then y, slice range, sample.  XCD x (= blockIdx % 8) owns a contiguous range of them
     // and its workgroups take them round-robin, so the workgroups running at the same time on an XCD walk
     // neighbouring columns and share their halos in that XCD's L2.
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };
 
     // ---- the slice stream.  The units of this workgroup form ONE stream of input slices: unit u contributes its
     // nz+2 slices (one above, one below the outputs; zero pages outside the volume), then the next unit follows.  The
@@ -458,32 +438,11 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll_t(const ConvArgs a, con
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {   // units = columns of the INPUT grid
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };   // units = columns of the INPUT grid
 
     const int ps0 = PARTS * a.C0;
     const int slice_elems = a.Hi * a.Wi * ps0;
@@ -731,32 +690,11 @@ __global__ __launch_bounds__(256) void conv_roll_t32(const ConvArgs a, const Rol
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {   // units = columns of the INPUT grid
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };   // units = columns of the INPUT grid
 
     const int ps0 = PARTS * a.C0;
     const int slice_elems = a.Hi * a.Wi * ps0;
@@ -1000,32 +938,11 @@ __global__ __launch_bounds__(256) void conv_roll_efd(const ConvArgs a, const Rol
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {   // columns of the OUTPUT grid
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };   // columns of the OUTPUT grid
 
     const int rec = PARTS * 8;
     const int xslice = a.Hi * a.Wi * rec, pslice = a.Ho * a.Wo * rec;
@@ -1228,14 +1145,8 @@ __global__ __launch_bounds__(NT * KH == 4 ? 512 : 256) void conv_roll_s2(const C
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -1429,76 +1340,74 @@ bool roll_lean(int prec, const ConvArgs &a, bool res_variant) {
     return prec == P_BF16X3 && (a.out || a.out_pre || a.cls_w) && !a.outf && !a.res1 && !a.res_bcast && a.relu != 2 && (res_variant || !a.res0) &&
            (a.Cout == 8 || a.Cout % 16 == 0) && !(a.dbg & DFFW_ARGS_NO_LEAN_ROLL);   // (the switch: generic epilogue, for A/B and the parity tests)
 }
-static const char *tf(bool b) { return b ? "true" : "false"; }
 
 void roll_tile(int *ty, int *tx) {
     *ty = DFFW_ROLL_TY;
     *tx = DFFW_ROLL_TX;
 }
 
+// The instantiation tables (KernelRow, dffw_persist.h).  Every family is laid out the same way: the split-bf16 rows first, indexed by the template
+// flags in the order the table's comment gives (false before true), then the fp16 and the bf16 rows (no residual prefetch, no lean epilogue there).
+#define ROLL_CFG DFFW_ROLL_TY, DFFW_ROLL_TX, DFFW_ROLL_NW, DFFW_ROLL_RING
+
+static const RollRow kRoll[] = {   // [res][pair][lean]; fp16 [pair]; bf16 [pair]
+#define R(...) DFFW_ROW(DFFW_ROLL_NW * 64, conv_roll, __VA_ARGS__)
+    R(0, ROLL_CFG, false, false, false), R(0, ROLL_CFG, false, false, true), R(0, ROLL_CFG, false, true, false), R(0, ROLL_CFG, false, true, true),
+    R(0, ROLL_CFG, true, false, false),  R(0, ROLL_CFG, true, false, true),  R(0, ROLL_CFG, true, true, false),  R(0, ROLL_CFG, true, true, true),
+    R(1, ROLL_CFG, false, false, false), R(1, ROLL_CFG, false, true, false), R(2, ROLL_CFG, false, false, false), R(2, ROLL_CFG, false, true, false),
+#undef R
+};
+static const RollRow *select_roll(int prec, const ConvArgs &a, bool pair) {
+    if (prec == P_FP16 || prec == P_BF16) return &kRoll[8 + 2 * (prec - 1) + pair];
+    if (prec != P_BF16X3) return nullptr;
+    // the hand-prefetched residual exists for the split-bf16 storage only; fp16/bf16 layers with a residual load it in the epilogue
+    const bool res = a.res0 != nullptr, lean = roll_lean(prec, a, true) && !a.cls_w;
+    return &kRoll[res * 4 + pair * 2 + lean];
+}
+
 void conv_roll_kernel_name(int prec, const ConvArgs &a, bool pair, char *buf, int n) {
     if (rollx_pair_ok(prec, a, pair)) return conv_rollx_pair_kernel_name(a, buf, n);
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    snprintf(buf, n, "dffw::conv_roll<%d, %d, %d, %d, %d, %s, %s, %s>", prec, DFFW_ROLL_TY, DFFW_ROLL_TX, DFFW_ROLL_NW, DFFW_ROLL_RING, tf(res), tf(pair),
-             tf(roll_lean(prec, a, true) && !a.cls_w));
+    copy_row_name(select_roll(prec, a, pair), buf, n);
 }
 
-void conv_roll_t_kernel_name(int prec, const ConvArgs &a, char *buf, int n) {
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    snprintf(buf, n, "dffw::conv_roll_t<%d, %d, %d, %d, %d, %s, %s>", prec, DFFW_ROLL_TY, DFFW_ROLL_TX, DFFW_ROLL_NW, DFFW_ROLL_RING, tf(res), tf(roll_lean(prec, a, true)));
+hipError_t launch_conv_roll(int prec, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
+    if (rollx_pair_ok(prec, a, t.pair != 0)) return launch_conv_rollx_pair(a, t, s);
+    // two resident workgroups per CU (72 KiB of LDS each)
+    return launch_row(select_roll(prec, a, t.pair != 0), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);
 }
 
+static const RollRow kRollT[] = {   // [res][lean]; fp16; bf16
+#define R(...) DFFW_ROW(DFFW_ROLL_NW * 64, conv_roll_t, __VA_ARGS__)
+    R(0, ROLL_CFG, false, false), R(0, ROLL_CFG, false, true), R(0, ROLL_CFG, true, false), R(0, ROLL_CFG, true, true),
+    R(1, ROLL_CFG, false, false), R(2, ROLL_CFG, false, false),
+#undef R
+};
+static const RollRow *select_roll_t(int prec, const ConvArgs &a) {
+    if (prec == P_FP16 || prec == P_BF16) return &kRollT[4 + (prec - 1)];
+    if (prec != P_BF16X3) return nullptr;
+    return &kRollT[(a.res0 != nullptr) * 2 + roll_lean(prec, a, true)];
+}
+void conv_roll_t_kernel_name(int prec, const ConvArgs &a, char *buf, int n) { copy_row_name(select_roll_t(prec, a), buf, n); }
 hipError_t launch_conv_roll_t(int prec, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 512;
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(DFFW_ROLL_NW * 64);
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    const bool lean = roll_lean(prec, a, true);
-#define DFFW_ROLLT_LAUNCH(P, R, L) hipLaunchKernelGGL((conv_roll_t<P, DFFW_ROLL_TY, DFFW_ROLL_TX, DFFW_ROLL_NW, DFFW_ROLL_RING, R, L>), grid, block, 0, s, a, t)
-    switch (prec) {
-        case P_BF16X3:
-            if (res && lean) DFFW_ROLLT_LAUNCH(P_BF16X3, true, true);
-            else if (res) DFFW_ROLLT_LAUNCH(P_BF16X3, true, false);
-            else if (lean) DFFW_ROLLT_LAUNCH(P_BF16X3, false, true);
-            else DFFW_ROLLT_LAUNCH(P_BF16X3, false, false);
-            break;
-        case P_FP16: DFFW_ROLLT_LAUNCH(P_FP16, false, false); break;
-        case P_BF16: DFFW_ROLLT_LAUNCH(P_BF16, false, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_ROLLT_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_roll_t(prec, a), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);   // 512: two resident workgroups per CU
 }
 
-void conv_roll_t32_kernel_name(int prec, int py, const ConvArgs &a, char *buf, int n) {
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    snprintf(buf, n, "dffw::conv_roll_t32<%d, %d, %d, %s, %s>", prec, py, py ? 6 : 4, tf(res), tf(roll_lean(prec, a, true)));
+static const RollRow kRollT32[] = {   // [py][res][lean]; fp16 [py]; bf16 [py]   (the ring is 4 slots deep for row phase 0, 6 for phase 1)
+#define R(...) DFFW_ROW(256, conv_roll_t32, __VA_ARGS__)
+    R(0, 0, 4, false, false), R(0, 0, 4, false, true), R(0, 0, 4, true, false), R(0, 0, 4, true, true),
+    R(0, 1, 6, false, false), R(0, 1, 6, false, true), R(0, 1, 6, true, false), R(0, 1, 6, true, true),
+    R(1, 0, 4, false, false), R(1, 1, 6, false, false), R(2, 0, 4, false, false), R(2, 1, 6, false, false),
+#undef R
+};
+static const RollRow *select_roll_t32(int prec, int py, const ConvArgs &a) {
+    py = py != 0;
+    if (prec == P_FP16 || prec == P_BF16) return &kRollT32[8 + 2 * (prec - 1) + py];
+    if (prec != P_BF16X3) return nullptr;
+    return &kRollT32[py * 4 + (a.res0 != nullptr) * 2 + roll_lean(prec, a, true)];
 }
-
+void conv_roll_t32_kernel_name(int prec, int py, const ConvArgs &a, char *buf, int n) { copy_row_name(select_roll_t32(prec, py, a), buf, n); }
 hipError_t launch_conv_roll_t32(int prec, int py, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 512;
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    const bool lean = roll_lean(prec, a, true);
-#define DFFW_T32_LAUNCH(P, R, L)                                                                      \
-    do {                                                                                              \
-        if (py) hipLaunchKernelGGL((conv_roll_t32<P, 1, 6, R, L>), grid, block, 0, s, a, t);         \
-        else hipLaunchKernelGGL((conv_roll_t32<P, 0, 4, R, L>), grid, block, 0, s, a, t);            \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3:
-            if (res && lean) DFFW_T32_LAUNCH(P_BF16X3, true, true);
-            else if (res) DFFW_T32_LAUNCH(P_BF16X3, true, false);
-            else if (lean) DFFW_T32_LAUNCH(P_BF16X3, false, true);
-            else DFFW_T32_LAUNCH(P_BF16X3, false, false);
-            break;
-        case P_FP16: DFFW_T32_LAUNCH(P_FP16, false, false); break;
-        case P_BF16: DFFW_T32_LAUNCH(P_BF16, false, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_T32_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_roll_t32(prec, py, a), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);   // 512: two resident workgroups per CU
 }
 
 void roll_t32_tile(int py, int *ty, int *tx) {
@@ -1511,32 +1420,20 @@ void efd_roll_tile(int *ty, int *tx) {
     *tx = 16;
 }
 
-void conv_roll_efd_kernel_name(int prec, const ConvArgs &a, bool dual, char *buf, int n) {
-    snprintf(buf, n, "dffw::conv_roll_efd<%d, %d, %s, %s>", prec, 5, tf(dual), tf(roll_lean(prec, a, false) && !a.cls_w));
+static const RollRow kRollEfd[] = {   // [dual][lean]; fp16 [dual]; bf16 [dual]
+#define R(...) DFFW_ROW(256, conv_roll_efd, __VA_ARGS__)
+    R(0, 5, false, false), R(0, 5, false, true), R(0, 5, true, false), R(0, 5, true, true),
+    R(1, 5, false, false), R(1, 5, true, false), R(2, 5, false, false), R(2, 5, true, false),
+#undef R
+};
+static const RollRow *select_roll_efd(int prec, const ConvArgs &a, bool dual) {
+    if (prec == P_FP16 || prec == P_BF16) return &kRollEfd[4 + 2 * (prec - 1) + dual];
+    if (prec != P_BF16X3) return nullptr;
+    return &kRollEfd[dual * 2 + (roll_lean(prec, a, false) && !a.cls_w)];
 }
-
+void conv_roll_efd_kernel_name(int prec, const ConvArgs &a, bool dual, char *buf, int n) { copy_row_name(select_roll_efd(prec, a, dual), buf, n); }
 hipError_t launch_conv_roll_efd(int prec, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 512;
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-    const bool dual = t.wroll2 != nullptr;
-    const bool lean = roll_lean(prec, a, false) && !a.cls_w;
-#define DFFW_EFD_LAUNCH(P, L)                                                                       \
-    do {                                                                                            \
-        if (dual) hipLaunchKernelGGL((conv_roll_efd<P, 5, true, L>), grid, block, 0, s, a, t);     \
-        else hipLaunchKernelGGL((conv_roll_efd<P, 5, false, L>), grid, block, 0, s, a, t);         \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3:
-            if (lean) DFFW_EFD_LAUNCH(P_BF16X3, true);
-            else DFFW_EFD_LAUNCH(P_BF16X3, false);
-            break;
-        case P_FP16: DFFW_EFD_LAUNCH(P_FP16, false); break;
-        case P_BF16: DFFW_EFD_LAUNCH(P_BF16, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_EFD_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_roll_efd(prec, a, t.wroll2 != nullptr), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);   // 512: two resident workgroups per CU
 }
 
 void s2_roll_tile(int nt, int *ty, int *tx) {
@@ -1544,66 +1441,25 @@ void s2_roll_tile(int nt, int *ty, int *tx) {
     *tx = nt == 2 ? 8 : 16;
 }
 
-void conv_roll_s2_kernel_name(int prec, int nt, int kh, const ConvArgs &a, char *buf, int n) {
-    snprintf(buf, n, "dffw::conv_roll_s2<%d, %d, %d, %d, %s>", prec, nt, kh, kh == 2 ? 5 : (nt == 2 ? 6 : 4), tf(roll_lean(prec, a, false) && !a.cls_w));
+// ring depth by LDS: 16 channels, 4 x 8 column: 10 KiB per slice -> 6 slots = 60 KiB (two workgroups per CU); 4 x 16 column:
+// 20 KiB -> 4 slots (two workgroups); 32 channels, 4 x 8 column, 8 waves: 24 KiB -> 5 slots + the exchange area = 128 KiB (one)
+static const RollRow kRollS2[] = {   // [form: kh 2 | nt 2 | nt 1][lean]; fp16 [form]; bf16 [form]
+#define R(block, ...) DFFW_ROW(block, conv_roll_s2, __VA_ARGS__)
+    R(512, 0, 2, 2, 5, false), R(512, 0, 2, 2, 5, true), R(256, 0, 2, 1, 6, false), R(256, 0, 2, 1, 6, true), R(256, 0, 1, 1, 4, false), R(256, 0, 1, 1, 4, true),
+    R(512, 1, 2, 2, 5, false), R(256, 1, 2, 1, 6, false), R(256, 1, 1, 1, 4, false),
+    R(512, 2, 2, 2, 5, false), R(256, 2, 2, 1, 6, false), R(256, 2, 1, 1, 4, false),
+#undef R
+};
+static const RollRow *select_roll_s2(int prec, int nt, int kh, const ConvArgs &a) {
+    const int form = kh == 2 ? 0 : nt == 2 ? 1 : 2;
+    if (prec == P_FP16 || prec == P_BF16) return &kRollS2[6 + 3 * (prec - 1) + form];
+    if (prec != P_BF16X3) return nullptr;
+    return &kRollS2[form * 2 + (roll_lean(prec, a, false) && !a.cls_w)];
 }
-
+void conv_roll_s2_kernel_name(int prec, int nt, int kh, const ConvArgs &a, char *buf, int n) { copy_row_name(select_roll_s2(prec, nt, kh, a), buf, n); }
 hipError_t launch_conv_roll_s2(int prec, int nt, int kh, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    // ring depth by LDS: 16 channels, 4 x 8 column: 10 KiB per slice -> 6 slots = 60 KiB (two workgroups per CU); 4 x 16 column:
-    // 20 KiB -> 4 slots (two workgroups); 32 channels, 4 x 8 column, 8 waves: 24 KiB -> 5 slots + the exchange area = 128 KiB (one)
-    const int want = t.wgs > 0 ? t.wgs : (kh == 2 ? 256 : 512);
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8))));
-    const bool lean = roll_lean(prec, a, false) && !a.cls_w;
-#define DFFW_S2_LAUNCH(P, L)                                                                                   \
-    do {                                                                                                       \
-        if (kh == 2) hipLaunchKernelGGL((conv_roll_s2<P, 2, 2, 5, L>), grid, dim3(512), 0, s, a, t);          \
-        else if (nt == 2) hipLaunchKernelGGL((conv_roll_s2<P, 2, 1, 6, L>), grid, dim3(256), 0, s, a, t);     \
-        else hipLaunchKernelGGL((conv_roll_s2<P, 1, 1, 4, L>), grid, dim3(256), 0, s, a, t);                  \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3:
-            if (lean) DFFW_S2_LAUNCH(P_BF16X3, true);
-            else DFFW_S2_LAUNCH(P_BF16X3, false);
-            break;
-        case P_FP16: DFFW_S2_LAUNCH(P_FP16, false); break;
-        case P_BF16: DFFW_S2_LAUNCH(P_BF16, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_S2_LAUNCH
-    return hipGetLastError();
+    return launch_row(select_roll_s2(prec, nt, kh, a), t.total_tiles, t.wgs > 0 ? t.wgs : (kh == 2 ? 256 : 512), 1, s, a, t);   // one / two resident workgroups per CU
 }
-
-hipError_t launch_conv_roll(int prec, const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    if (rollx_pair_ok(prec, a, t.pair != 0)) return launch_conv_rollx_pair(a, t, s);
-    // persistent grid: two resident workgroups per CU (72 KiB of LDS each), a multiple of the 8 XCDs, never more
-    // workgroups than an XCD has columns
-    const int want = t.wgs > 0 ? t.wgs : 512;
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(DFFW_ROLL_NW * 64);
-    // the hand-prefetched residual exists for the split-bf16 storage only; fp16/bf16 layers with a residual load it in the epilogue
-    const bool res = a.res0 != nullptr && prec == P_BF16X3;
-    const bool lean = roll_lean(prec, a, true) && !a.cls_w;
-#define DFFW_ROLL_LAUNCH(P, R, Q, L) hipLaunchKernelGGL((conv_roll<P, DFFW_ROLL_TY, DFFW_ROLL_TX, DFFW_ROLL_NW, DFFW_ROLL_RING, R, Q, L>), grid, block, 0, s, a, t)
-#define DFFW_ROLL_LAUNCH_Q(P, R, L)                   \
-    do {                                              \
-        if (t.pair) DFFW_ROLL_LAUNCH(P, R, true, L);  \
-        else DFFW_ROLL_LAUNCH(P, R, false, L);        \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3:
-            if (res && lean) DFFW_ROLL_LAUNCH_Q(P_BF16X3, true, true);
-            else if (res) DFFW_ROLL_LAUNCH_Q(P_BF16X3, true, false);
-            else if (lean) DFFW_ROLL_LAUNCH_Q(P_BF16X3, false, true);
-            else DFFW_ROLL_LAUNCH_Q(P_BF16X3, false, false);
-            break;
-        case P_FP16: DFFW_ROLL_LAUNCH_Q(P_FP16, false, false); break;
-        case P_BF16: DFFW_ROLL_LAUNCH_Q(P_BF16, false, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_ROLL_LAUNCH_Q
-#undef DFFW_ROLL_LAUNCH
-    return hipGetLastError();
-}
+#undef ROLL_CFG
 
 }  // namespace dffw

@@ -31,6 +31,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -87,6 +88,7 @@ __device__ __forceinline__ void rollk_body(const ConvArgs &a, const RollArgs &t,
     const int myu = wave & 3;                      // the unit of a half-step this wave owns (if it owns one): operand tile myu >> 1, output tile myu & 1
 
     // ---- this workgroup's units (8 x 8 columns of one sample / slice range): XCD x owns a contiguous range, as conv_roll -------------
+    // (inline copy of persistent_range(), dffw_persist.h: through the helper hipcc allocates this kernel's registers differently)
     const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
     int ufirst, uend;
     {
@@ -96,6 +98,7 @@ __device__ __forceinline__ void rollk_body(const ConvArgs &a, const RollArgs &t,
         ufirst = xs + widx;
     }
     if (ufirst >= uend) return;
+    // (... and of roll_unit())
     struct Unit {
         int b, zbeg, nz, gy0, gx0;
     };
@@ -563,56 +566,41 @@ int rollk_waves(int prec, const ConvArgs &a) {
     return cin / 8;
 }
 
-hipError_t launch_conv_rollk(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
+#define R(nw, ...) DFFW_ROW(nw * 64, conv_rollk, nw, __VA_ARGS__)
+static const RollRow kRollk[] = {   // [8 | 4 waves][relu][res]   (the names carry the defaulted ABL and SKEW: the kernel symbols, which tools/ match)
+    R(8, false, false, 0, DFFW_ROLLK_SKEW), R(8, false, true, 0, DFFW_ROLLK_SKEW), R(8, true, false, 0, DFFW_ROLLK_SKEW), R(8, true, true, 0, DFFW_ROLLK_SKEW),
+    R(4, false, false, 0, DFFW_ROLLK_SKEW), R(4, false, true, 0, DFFW_ROLLK_SKEW), R(4, true, false, 0, DFFW_ROLLK_SKEW), R(4, true, true, 0, DFFW_ROLLK_SKEW),
+};
+#ifdef DFFW_ABL_BUILD   // development (make ABL=1): timing ablations of the two most used instantiations, relu without residual (results are wrong)
+#define RS(S) {S, R(8, true, false, 0, S)}
+static const AblRow<RollRow> kRollkSkew[] = {RS(0), RS(1), RS(3), RS(4), RS(6)};   // DFFW_ROLLK_SKEW, 8 waves
+#undef RS
+#define RA(nw, A) {A, R(nw, true, false, A, DFFW_ROLLK_SKEW)}
+static const AblRow<RollRow> kRollkAbl8[] = {RA(8, 1), RA(8, 2), RA(8, 3), RA(8, 4), RA(8, 8), RA(8, 16), RA(8, 24), RA(8, 32), RA(8, 44), RA(8, 47), RA(8, 63)};   // DFFW_ROLLK_ABL
+static const AblRow<RollRow> kRollkAbl4[] = {RA(4, 1), RA(4, 2), RA(4, 3), RA(4, 4), RA(4, 8), RA(4, 16), RA(4, 24), RA(4, 32), RA(4, 44), RA(4, 47), RA(4, 63)};
+#undef RA
+#endif
+#undef R
+static const RollRow *select_rollk(const ConvArgs &a) {
     const int nw = (a.C0 + a.C1) / 8;
-    const int ny = t.pair < 0 ? a.Cout / 32 : 1;                  // (RollArgs::pair < 0: every 32-channel output half in ONE launch, as grid.y)
-    const int want = (t.wgs > 0 ? t.wgs : (nw == 8 ? 256 : 512)) / ny;   // 16 waves per CU either way
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8))), (unsigned)ny), block(nw * 64);
     const bool relu = a.relu == 1, res = a.res0 != nullptr;
-#define DFFW_ROLLK_LAUNCH(NW, RL, RS) hipLaunchKernelGGL((conv_rollk<NW, RL, RS>), grid, block, 0, s, a, t)
-#ifdef DFFW_ABL_BUILD   // development (make ABL=1): timing ablations of the two most used instantiations (results are wrong)
-    if (const char *z = getenv("DFFW_ROLLK_SKEW")) {
-        const int sk = atoi(z);
-        if (nw == 8 && relu && !res) {
-            if (sk == 0) { hipLaunchKernelGGL((conv_rollk<8, true, false, 0, 0>), grid, block, 0, s, a, t); return hipGetLastError(); }
-            if (sk == 1) { hipLaunchKernelGGL((conv_rollk<8, true, false, 0, 1>), grid, block, 0, s, a, t); return hipGetLastError(); }
-            if (sk == 3) { hipLaunchKernelGGL((conv_rollk<8, true, false, 0, 3>), grid, block, 0, s, a, t); return hipGetLastError(); }
-            if (sk == 4) { hipLaunchKernelGGL((conv_rollk<8, true, false, 0, 4>), grid, block, 0, s, a, t); return hipGetLastError(); }
-            if (sk == 6) { hipLaunchKernelGGL((conv_rollk<8, true, false, 0, 6>), grid, block, 0, s, a, t); return hipGetLastError(); }
-        }
-    }
-    if (const char *z = getenv("DFFW_ROLLK_ABL")) {
-        const int abl = atoi(z);
-#define DFFW_ROLLK_ABL_CASE(A)                                                                                  \
-    if (abl == A && relu && !res) {                                                                             \
-        if (nw == 8) hipLaunchKernelGGL((conv_rollk<8, true, false, A>), grid, block, 0, s, a, t);             \
-        else hipLaunchKernelGGL((conv_rollk<4, true, false, A>), grid, block, 0, s, a, t);                     \
-        return hipGetLastError();                                                                               \
-    }
-        DFFW_ROLLK_ABL_CASE(1) DFFW_ROLLK_ABL_CASE(2) DFFW_ROLLK_ABL_CASE(3) DFFW_ROLLK_ABL_CASE(4) DFFW_ROLLK_ABL_CASE(8) DFFW_ROLLK_ABL_CASE(16)
-        DFFW_ROLLK_ABL_CASE(24) DFFW_ROLLK_ABL_CASE(32) DFFW_ROLLK_ABL_CASE(44) DFFW_ROLLK_ABL_CASE(47) DFFW_ROLLK_ABL_CASE(63)
-#undef DFFW_ROLLK_ABL_CASE
+#ifdef DFFW_ABL_BUILD
+    if (relu && !res) {
+        const RollRow *row = nw == 8 ? abl_row(kRollkSkew, "DFFW_ROLLK_SKEW") : nullptr;
+        if (!row) row = nw == 8 ? abl_row(kRollkAbl8, "DFFW_ROLLK_ABL") : abl_row(kRollkAbl4, "DFFW_ROLLK_ABL");
+        if (row) return row;
     }
 #endif
-    if (nw == 8) {
-        if (relu && res) DFFW_ROLLK_LAUNCH(8, true, true);
-        else if (relu) DFFW_ROLLK_LAUNCH(8, true, false);
-        else if (res) DFFW_ROLLK_LAUNCH(8, false, true);
-        else DFFW_ROLLK_LAUNCH(8, false, false);
-    } else {
-        if (relu && res) DFFW_ROLLK_LAUNCH(4, true, true);
-        else if (relu) DFFW_ROLLK_LAUNCH(4, true, false);
-        else if (res) DFFW_ROLLK_LAUNCH(4, false, true);
-        else DFFW_ROLLK_LAUNCH(4, false, false);
-    }
-#undef DFFW_ROLLK_LAUNCH
-    return hipGetLastError();
+    return &kRollk[(nw != 8) * 4 + relu * 2 + res];
 }
 
-void conv_rollk_kernel_name(const ConvArgs &a, char *buf, int n) {
-    // (rocprofv3's spelling, defaulted template arguments included: tools/hbm_traffic.py and the PMC summaries match kernels by name)
-    snprintf(buf, n, "dffw::conv_rollk<%d, %s, %s, 0, %d>", (a.C0 + a.C1) / 8, a.relu == 1 ? "true" : "false", a.res0 ? "true" : "false", DFFW_ROLLK_SKEW);
+hipError_t launch_conv_rollk(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
+    const RollRow *row = select_rollk(a);
+    const int ny = t.pair < 0 ? a.Cout / 32 : 1;                  // (RollArgs::pair < 0: every 32-channel output half in ONE launch, as grid.y)
+    const int want = (t.wgs > 0 ? t.wgs : (row->block == 512 ? 256 : 512)) / ny;   // 16 waves per CU either way
+    return launch_row(row, t.total_tiles, want, ny, s, a, t);
 }
+
+void conv_rollk_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(select_rollk(a), buf, n); }
 
 }  // namespace dffw

@@ -28,6 +28,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -94,6 +95,7 @@ __device__ __forceinline__ void rollt_body(const ConvArgs &a, const RollArgs &t,
     const bool relu = a.relu == 1;
 
     // ---- this workgroup's units (8 x 8 columns of one sample's input grid): XCD x owns a contiguous range, as conv_roll -------------
+    // (inline copy of persistent_range(), dffw_persist.h: through the helper hipcc allocates this kernel's registers differently)
     const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
     int ufirst, uend;
     {
@@ -455,37 +457,24 @@ bool rollt_ok(int prec, const ConvArgs &a) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * a.C0 * 4 < (1ll << 31) && (int64_t)a.Ho * a.Wo * a.Cout * 4 < (1ll << 31);
 }
 
-hipError_t launch_conv_rollt(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const bool wide = rollt_wide(a);
-    const int nw = wide ? 8 : a.C0 / 8, ny = wide ? 1 : a.Cout / 32;
-    const int want = (t.wgs > 0 ? t.wgs : (nw == 8 ? 256 : 512)) / ny;   // 16 waves per CU either way
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8))), (unsigned)ny), block(nw * 64);
-    const int mode = rollt_mode(a);
-#define DFFW_ROLLT_LAUNCH(CI, MD, WD) hipLaunchKernelGGL((conv_rollt<CI, MD, WD>), grid, block, 0, s, a, t)
-    if (wide && a.C0 == 16) {
-        if (mode == 2) DFFW_ROLLT_LAUNCH(16, 2, true);
-        else if (mode == 1) DFFW_ROLLT_LAUNCH(16, 1, true);
-        else DFFW_ROLLT_LAUNCH(16, 0, true);
-    } else if (wide) {
-        if (mode == 2) DFFW_ROLLT_LAUNCH(32, 2, true);
-        else if (mode == 1) DFFW_ROLLT_LAUNCH(32, 1, true);
-        else DFFW_ROLLT_LAUNCH(32, 0, true);
-    } else if (nw == 8) {
-        if (mode == 2) DFFW_ROLLT_LAUNCH(64, 2, false);
-        else if (mode == 1) DFFW_ROLLT_LAUNCH(64, 1, false);
-        else DFFW_ROLLT_LAUNCH(64, 0, false);
-    } else {
-        if (mode == 2) DFFW_ROLLT_LAUNCH(32, 2, false);
-        else if (mode == 1) DFFW_ROLLT_LAUNCH(32, 1, false);
-        else DFFW_ROLLT_LAUNCH(32, 0, false);
-    }
-#undef DFFW_ROLLT_LAUNCH
-    return hipGetLastError();
+#define R(block, ...) DFFW_ROW(block, conv_rollt, __VA_ARGS__)
+static const RollRow kRollt[] = {   // [16 -> 16 wide | 32 -> 16 wide | 64 input channels | 32][mode]
+    R(512, 16, 0, true),  R(512, 16, 1, true),  R(512, 16, 2, true),  R(512, 32, 0, true),  R(512, 32, 1, true),  R(512, 32, 2, true),
+    R(512, 64, 0, false), R(512, 64, 1, false), R(512, 64, 2, false), R(256, 32, 0, false), R(256, 32, 1, false), R(256, 32, 2, false),
+};
+#undef R
+static const RollRow *select_rollt(const ConvArgs &a) {
+    const int form = rollt_wide(a) ? (a.C0 == 16 ? 0 : 1) : (a.C0 == 64 ? 2 : 3);
+    return &kRollt[form * 3 + rollt_mode(a)];
 }
 
-void conv_rollt_kernel_name(const ConvArgs &a, char *buf, int n) {
-    snprintf(buf, n, "dffw::conv_rollt<%d, %d, %s>", a.C0, rollt_mode(a), rollt_wide(a) ? "true" : "false");
+hipError_t launch_conv_rollt(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
+    const RollRow *row = select_rollt(a);
+    const int ny = rollt_wide(a) ? 1 : a.Cout / 32;
+    const int want = (t.wgs > 0 ? t.wgs : (row->block == 512 ? 256 : 512)) / ny;   // 16 waves per CU either way
+    return launch_row(row, t.total_tiles, want, ny, s, a, t);
 }
+
+void conv_rollt_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(select_rollt(a), buf, n); }
 
 }  // namespace dffw

@@ -26,6 +26,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -52,32 +53,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int g = lane >> 4, r = lane & 15;
 
     // ---- this workgroup's units (columns of one sample / slice range), as conv_roll: XCD x owns a contiguous range -------------
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };
 
     // ---- fill: this wave's three pieces of a slice belong to ONE source (waves 0-1: in0 / channel octet 0, waves 2-3: in1 / octet 1) ----
     const bool two = a.C1 != 0;                        // virtual concat of two 8-channel tensors (else one 16-channel tensor)
@@ -347,32 +327,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int half = wave >> 2, wq = wave & 3;          // K half (= source tensor of a concat) and the pair of rows this wave contracts
     const int g = lane >> 4, r = lane & 15;
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
-    struct Unit {
-        int b, zbeg, nz, gy0, gx0;
-    };
-    auto decode = [&](int u) {
-        Unit c;
-        const int txi = u % t.tiles_x;
-        int tt = u / t.tiles_x;
-        const int tyi = tt % t.tiles_y;
-        tt /= t.tiles_y;
-        const int zp = tt % t.zsplit;
-        c.b = tt / t.zsplit;
-        c.gy0 = tyi * TY;
-        c.gx0 = txi * TX;
-        c.zbeg = zp * a.No / t.zsplit;
-        c.nz = (zp + 1) * a.No / t.zsplit - c.zbeg;
-        return c;
-    };
+    using Unit = RollUnit;
+    auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };
 
     // ---- fill: a wave's three pieces belong to its own half (waves 0-3: in0 / channels 0-15, waves 4-7: in1 / channels 16-31) ----
     const bool two = a.C1 != 0;
@@ -610,16 +569,11 @@ bool rollx_k2_ok(int prec, const ConvArgs &a) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * recb < (1ll << 31);
 }
 
+static const RollRow kRollxK2[] = {DFFW_ROW(rollk2::NW * 64, conv_rollx_k2, false), DFFW_ROW(rollk2::NW * 64, conv_rollx_k2, true)};   // [relu]
 hipError_t launch_conv_rollx_k2(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 256;   // one 8-wave workgroup per CU
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(rollk2::NW * 64);
-    if (a.relu == 1) hipLaunchKernelGGL((conv_rollx_k2<true>), grid, block, 0, s, a, t);
-    else hipLaunchKernelGGL((conv_rollx_k2<false>), grid, block, 0, s, a, t);
-    return hipGetLastError();
+    return launch_row(&kRollxK2[a.relu == 1], t.total_tiles, t.wgs > 0 ? t.wgs : 256, 1, s, a, t);   // 256: one 8-wave workgroup per CU
 }
-
-void conv_rollx_k2_kernel_name(const ConvArgs &a, char *buf, int n) { snprintf(buf, n, "dffw::conv_rollx_k2<%s>", a.relu == 1 ? "true" : "false"); }
+void conv_rollx_k2_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(&kRollxK2[a.relu == 1], buf, n); }
 
 bool rollx_pair_ok(int prec, const ConvArgs &a, bool pair) {
     if (prec != P_BF16X3 || !pair || (a.dbg & DFFW_ARGS_NO_ROLLX)) return false;
@@ -630,20 +584,28 @@ bool rollx_pair_ok(int prec, const ConvArgs &a, bool pair) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * recb < (1ll << 31);
 }
 
-hipError_t launch_conv_rollx_pair(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 512;
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(rollx::NW * 64);
-    if (a.relu != 1) hipLaunchKernelGGL((conv_rollx_pair<false>), grid, block, 0, s, a, t);
+static const RollRow kRollxPair[] = {   // [relu]
+    // labels, not the symbols (which end in the defaulted ", 0, false"): the spelling the dispatch pins and the profile tools were recorded with
+    {"dffw::conv_rollx_pair<false>", conv_rollx_pair<false>, rollx::NW * 64},
+    {"dffw::conv_rollx_pair<true>", conv_rollx_pair<true>, rollx::NW * 64},
 #ifdef DFFW_ABL_BUILD   // development (make ABL=1): timing ablations (DFFW_ROLLX_ABL; results are wrong with any bit set), non-temporal stores (DFFW_ROLLX_NTS)
-    else if (getenv("DFFW_ROLLX_ABL") && atoi(getenv("DFFW_ROLLX_ABL")) == 3) hipLaunchKernelGGL((conv_rollx_pair<true, 3>), grid, block, 0, s, a, t);
-    else if (getenv("DFFW_ROLLX_ABL") && atoi(getenv("DFFW_ROLLX_ABL")) == 12) hipLaunchKernelGGL((conv_rollx_pair<true, 12>), grid, block, 0, s, a, t);
-    else if (getenv("DFFW_ROLLX_NTS")) hipLaunchKernelGGL((conv_rollx_pair<true, 0, true>), grid, block, 0, s, a, t);
+    DFFW_ROW(rollx::NW * 64, conv_rollx_pair, true, 3, false), DFFW_ROW(rollx::NW * 64, conv_rollx_pair, true, 12, false),
+    DFFW_ROW(rollx::NW * 64, conv_rollx_pair, true, 0, true),
 #endif
-    else hipLaunchKernelGGL((conv_rollx_pair<true>), grid, block, 0, s, a, t);
-    return hipGetLastError();
+};
+static const RollRow *select_rollx_pair(const ConvArgs &a) {
+    if (a.relu != 1) return &kRollxPair[0];
+#ifdef DFFW_ABL_BUILD
+    const char *z = getenv("DFFW_ROLLX_ABL");
+    const int abl = z ? atoi(z) : 0;
+    if (abl == 3 || abl == 12) return &kRollxPair[abl == 3 ? 2 : 3];
+    if (getenv("DFFW_ROLLX_NTS")) return &kRollxPair[4];
+#endif
+    return &kRollxPair[1];
 }
-
-void conv_rollx_pair_kernel_name(const ConvArgs &a, char *buf, int n) { snprintf(buf, n, "dffw::conv_rollx_pair<%s>", a.relu == 1 ? "true" : "false"); }
+hipError_t launch_conv_rollx_pair(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
+    return launch_row(select_rollx_pair(a), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);   // 512: two resident workgroups per CU
+}
+void conv_rollx_pair_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(select_rollx_pair(a), buf, n); }
 
 }  // namespace dffw

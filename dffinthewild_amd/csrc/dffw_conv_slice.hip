@@ -23,6 +23,7 @@
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -52,14 +53,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int g = lane >> 4, r = lane & 15;
 
     // ---- this workgroup's units (8 x 16 columns of one sample): XCD x owns a contiguous range, as conv_roll -------------
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -362,14 +357,8 @@ __device__ __forceinline__ void slice64_body(const ConvArgs &a, const RollArgs &
     const int g = lane >> 4, r = lane & 15;
     const int nt = wave & (L::NTW - 1), rh = wave / L::NTW;   // (CAT: rh = row pair 0..3)
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -668,23 +657,16 @@ bool slice32_ok(int prec, const ConvArgs &a) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * 128 < (1ll << 31);
 }
 
+static const RollRow kSlice32[] = {   // [relu][res], then the row-sums variant
+#define R(...) DFFW_ROW(slice32::NW * 64, conv_slice32, __VA_ARGS__)
+    R(false, false, false), R(false, true, false), R(true, false, false), R(true, true, false), R(true, false, true),
+#undef R
+};
+static const RollRow *select_slice32(const ConvArgs &a) { return &kSlice32[(a.dbg & DFFW_ARGS_SUMS) ? 4 : (a.relu == 1) * 2 + (a.res0 != nullptr)]; }
 hipError_t launch_conv_slice32(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 512;   // two 4-wave workgroups per CU
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(slice32::NW * 64);
-    const bool relu = a.relu == 1, res = a.res0 != nullptr;
-    if (a.dbg & DFFW_ARGS_SUMS) hipLaunchKernelGGL((conv_slice32<true, false, true>), grid, block, 0, s, a, t);
-    else if (relu && res) hipLaunchKernelGGL((conv_slice32<true, true>), grid, block, 0, s, a, t);
-    else if (relu) hipLaunchKernelGGL((conv_slice32<true, false>), grid, block, 0, s, a, t);
-    else if (res) hipLaunchKernelGGL((conv_slice32<false, true>), grid, block, 0, s, a, t);
-    else hipLaunchKernelGGL((conv_slice32<false, false>), grid, block, 0, s, a, t);
-    return hipGetLastError();
+    return launch_row(select_slice32(a), t.total_tiles, t.wgs > 0 ? t.wgs : 512, 1, s, a, t);   // 512: two 4-wave workgroups per CU
 }
-
-void conv_slice32_kernel_name(const ConvArgs &a, char *buf, int n) {
-    if (a.dbg & DFFW_ARGS_SUMS) snprintf(buf, n, "dffw::conv_slice32<true, false, true>");
-    else snprintf(buf, n, "dffw::conv_slice32<%s, %s, false>", a.relu == 1 ? "true" : "false", a.res0 ? "true" : "false");   // (rocprofv3's spelling)
-}
+void conv_slice32_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(select_slice32(a), buf, n); }
 
 bool slice64_ok(int prec, const ConvArgs &a) {
     if (prec != P_BF16X3 || (a.dbg & DFFW_ARGS_NO_SLICE32)) return false;
@@ -700,26 +682,19 @@ bool slice64_ok(int prec, const ConvArgs &a) {
     return (int64_t)(a.Ni + 1) * a.Hi * a.Wi * 256 < (1ll << 31) && (int64_t)a.Ho * a.Wo * 256 < (1ll << 31);
 }
 
+static const RollRow kSlice64[] = {   // [cat | head | plain][relu], then the plain form's row-sums variant
+    DFFW_ROW(slice64::NW * 64, conv_slice32_cat, false),  DFFW_ROW(slice64::NW * 64, conv_slice32_cat, true),
+    DFFW_ROW(slice64::NW * 64, conv_slice64_head, false), DFFW_ROW(slice64::NW * 64, conv_slice64_head, true),
+    DFFW_ROW(slice64::NW * 64, conv_slice64, false, false), DFFW_ROW(slice64::NW * 64, conv_slice64, true, false),
+    DFFW_ROW(slice64::NW * 64, conv_slice64, true, true),
+};
+static const RollRow *select_slice64(const ConvArgs &a) {
+    const int form = a.C1 == 32 ? 0 : a.res_bcast ? 1 : 2;
+    return &kSlice64[form == 2 && (a.dbg & DFFW_ARGS_SUMS) ? 6 : form * 2 + (a.relu == 1)];
+}
 hipError_t launch_conv_slice64(const ConvArgs &a, const RollArgs &t, hipStream_t s) {
-    const int want = t.wgs > 0 ? t.wgs : 256;   // one 8-wave workgroup per CU
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(slice64::NW * 64);
-    if (a.C1 == 32) {
-        if (a.relu == 1) hipLaunchKernelGGL((conv_slice32_cat<true>), grid, block, 0, s, a, t);
-        else hipLaunchKernelGGL((conv_slice32_cat<false>), grid, block, 0, s, a, t);
-    } else if (a.res_bcast) {
-        if (a.relu == 1) hipLaunchKernelGGL((conv_slice64_head<true>), grid, block, 0, s, a, t);
-        else hipLaunchKernelGGL((conv_slice64_head<false>), grid, block, 0, s, a, t);
-    } else if (a.dbg & DFFW_ARGS_SUMS) hipLaunchKernelGGL((conv_slice64<true, true>), grid, block, 0, s, a, t);
-    else if (a.relu == 1) hipLaunchKernelGGL((conv_slice64<true, false>), grid, block, 0, s, a, t);
-    else hipLaunchKernelGGL((conv_slice64<false, false>), grid, block, 0, s, a, t);
-    return hipGetLastError();
+    return launch_row(select_slice64(a), t.total_tiles, t.wgs > 0 ? t.wgs : 256, 1, s, a, t);   // 256: one 8-wave workgroup per CU
 }
-
-void conv_slice64_kernel_name(const ConvArgs &a, char *buf, int n) {
-    if (a.C1 == 32) snprintf(buf, n, "dffw::conv_slice32_cat<%s>", a.relu == 1 ? "true" : "false");
-    else if (a.res_bcast) snprintf(buf, n, "dffw::conv_slice64_head<%s>", a.relu == 1 ? "true" : "false");
-    else snprintf(buf, n, "dffw::conv_slice64<%s, %s>", (a.dbg & DFFW_ARGS_SUMS) || a.relu == 1 ? "true" : "false", (a.dbg & DFFW_ARGS_SUMS) ? "true" : "false");
-}
+void conv_slice64_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(select_slice64(a), buf, n); }
 
 }  // namespace dffw

@@ -31,9 +31,12 @@
 #include <type_traits>
 
 #include "dffw_device.h"
+#include "dffw_persist.h"
 #include "dffw_srd_roll.h"
 
 namespace dffw {
+
+using SrdRow = KernelRow<SrdArgs>;   // dffw_persist.h
 
 // ABL (development only, DFFW_SRD_ABL): timing ablations -- 1 no stage C, 2 no stage A, 4 no stage B, 8 no fill, 16 no barriers, 32 no global stores
 template <int PREC, bool POOL, int ABL = 0>
@@ -71,14 +74,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     auto lds_store16 = [&](unsigned byte_off, f32x4 v) { asm volatile("ds_write_b128 %0, %1" ::"v"(lds0 + byte_off), "v"(v) : "memory"); };
 
     // ---- columns of this workgroup: as conv_roll (XCD-contiguous ranges, round-robin inside the XCD) ----------------
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -469,14 +466,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     };
     auto lds_store16 = [&](unsigned byte_off, f32x4 v) { asm volatile("ds_write_b128 %0, %1" ::"v"(lds0 + byte_off), "v"(v) : "memory"); };
 
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int ufirst, uend;
-    {
-        const int q = a.total_tiles >> 3, rem = a.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        uend = xs + q + (xcd < rem ? 1 : 0);
-        ufirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(a.total_tiles);   // dffw_persist.h
+    const int ufirst = ur.first, uend = ur.end, wgs_per_xcd = ur.step;
     if (ufirst >= uend) return;
     struct Unit {
         int b, gy0, gx0;
@@ -862,6 +853,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     };
     auto lds_store16 = [&](unsigned byte_off, f32x4 v) { asm volatile("ds_write_b128 %0, %1" ::"v"(lds0 + byte_off), "v"(v) : "memory"); };
 
+    // (inline copy of persistent_range(), dffw_persist.h: through the helper hipcc allocates this kernel's registers differently)
     const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
     int ufirst, uend;
     {
@@ -1371,120 +1363,66 @@ void srd_roll_tile(int *ty, int *tx) {
     *tx = 16;
 }
 
-void srd_roll_kernel_name(int prec, bool pool, char *buf, int n) { snprintf(buf, n, "dffw::srd_roll_kernel<%d, %s>", prec, pool ? "true" : "false"); }
+// The three fused blocks' tables: [prec][plain | pooled]; beside them (make ABL=1) the timing ablations of the split-bf16 pooled form, selected
+// with DFFW_SRD_ABL (wrong results with any bit set).  The production rows' names are labels, not the symbols (which end in the defaulted ", 0"): the
+// spelling the dispatch pins and the profile tools were recorded with; srd_pipe16's always carried it.
+#define DFFW_SRD_ROWS(kernel, P)                                                                      \
+    {"dffw::" #kernel "<" #P ", false>", kernel<P, false>, 256}, {"dffw::" #kernel "<" #P ", true>", kernel<P, true>, 256}
+
+static const KernelRow<SrdArgs, const float *, const float *> kSrdRoll[] = {
+    DFFW_SRD_ROWS(srd_roll_kernel, 0), DFFW_SRD_ROWS(srd_roll_kernel, 1), DFFW_SRD_ROWS(srd_roll_kernel, 2),
+};
+#ifdef DFFW_ABL_BUILD
+#define R(A) {A, DFFW_ROW(256, srd_roll_kernel, 0, true, A)}
+static const AblRow<KernelRow<SrdArgs, const float *, const float *>> kSrdRollAbl[] = {R(1), R(2), R(4), R(6), R(7), R(8), R(16), R(32), R(40), R(23)};
+#undef R
+#endif
+static const KernelRow<SrdArgs, const float *, const float *> *select_srd_roll(int prec, bool pool) {
+#ifdef DFFW_ABL_BUILD
+    if (prec == P_BF16X3 && pool)
+        if (const auto *row = abl_row(kSrdRollAbl, "DFFW_SRD_ABL")) return row;
+#endif
+    return prec_row(kSrdRoll, prec, 2, pool);
+}
+void srd_roll_kernel_name(int prec, bool pool, char *buf, int n) { copy_row_name(select_srd_roll(prec, pool), buf, n); }
+hipError_t launch_srd_roll(int prec, const SrdArgs &a, hipStream_t s) {
+    return launch_row(select_srd_roll(prec, a.pooled != nullptr), a.total_tiles, a.wgs > 0 ? a.wgs : 768, 1, s, a, a.w3, a.w1);   // 768: three resident workgroups per CU
+}
 
 void srd_roll16_tile(int *ty, int *tx) {
     *ty = 4;
     *tx = 16;
 }
 
-void srd_roll16_kernel_name(int prec, bool pool, char *buf, int n) { snprintf(buf, n, "dffw::srd_roll16_kernel<%d, %s>", prec, pool ? "true" : "false"); }
-void srd_pipe16_kernel_name(int prec, bool pool, char *buf, int n) { snprintf(buf, n, "dffw::srd_pipe16_kernel<%d, %s, 0>", prec, pool ? "true" : "false"); }
-
-hipError_t launch_srd_pipe16(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 512;   // two resident workgroups per CU
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-#define DFFW_SRDP16_LAUNCH(P)                                                                     \
-    do {                                                                                          \
-        if (a.pooled) hipLaunchKernelGGL((srd_pipe16_kernel<P, true>), grid, block, 0, s, a);     \
-        else hipLaunchKernelGGL((srd_pipe16_kernel<P, false>), grid, block, 0, s, a);             \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3: DFFW_SRDP16_LAUNCH(P_BF16X3); break;
-        case P_FP16: DFFW_SRDP16_LAUNCH(P_FP16); break;
-        case P_BF16: DFFW_SRDP16_LAUNCH(P_BF16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_SRDP16_LAUNCH
-    return hipGetLastError();
+static const SrdRow kSrdRoll16[] = {
+    DFFW_SRD_ROWS(srd_roll16_kernel, 0), DFFW_SRD_ROWS(srd_roll16_kernel, 1), DFFW_SRD_ROWS(srd_roll16_kernel, 2),
+};
+#ifdef DFFW_ABL_BUILD
+#define R(A) {A, DFFW_ROW(256, srd_roll16_kernel, 0, true, A)}
+static const AblRow<SrdRow> kSrdRoll16Abl[] = {R(1), R(2), R(4), R(6), R(7), R(8), R(16), R(32), R(40), R(23)};
+#undef R
+#endif
+static const SrdRow *select_srd_roll16(int prec, bool pool) {
+#ifdef DFFW_ABL_BUILD
+    if (prec == P_BF16X3 && pool)
+        if (const SrdRow *row = abl_row(kSrdRoll16Abl, "DFFW_SRD_ABL")) return row;
+#endif
+    return prec_row(kSrdRoll16, prec, 2, pool);
 }
-
+void srd_roll16_kernel_name(int prec, bool pool, char *buf, int n) { copy_row_name(select_srd_roll16(prec, pool), buf, n); }
 hipError_t launch_srd_roll16(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 512;   // two resident workgroups per CU
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-#ifdef DFFW_ABL_BUILD   // development (make ABL=1): timing ablations, selected with DFFW_SRD_ABL (wrong results with any bit set)
-    const char *az = getenv("DFFW_SRD_ABL");
-    const int abl = az ? atoi(az) : 0;
-#define DFFW_SRD16_ABL_CASES                                                                                      \
-    case 1: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 1>), grid, block, 0, s, a); break;              \
-    case 2: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 2>), grid, block, 0, s, a); break;              \
-    case 4: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 4>), grid, block, 0, s, a); break;              \
-    case 7: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 7>), grid, block, 0, s, a); break;              \
-    case 8: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 8>), grid, block, 0, s, a); break;              \
-    case 16: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 16>), grid, block, 0, s, a); break;            \
-    case 32: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 32>), grid, block, 0, s, a); break;            \
-    case 40: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 40>), grid, block, 0, s, a); break;            \
-    case 23: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 23>), grid, block, 0, s, a); break;            \
-    case 6: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true, 6>), grid, block, 0, s, a); break;
-#else
-    const int abl = 0;
-#define DFFW_SRD16_ABL_CASES
-#endif
-#define DFFW_SRD16_LAUNCH(P)                                                                \
-    do {                                                                                    \
-        if (a.pooled && P == P_BF16X3 && abl) {                                             \
-            switch (abl) {                                                                  \
-                DFFW_SRD16_ABL_CASES                                                        \
-                default: hipLaunchKernelGGL((srd_roll16_kernel<P_BF16X3, true>), grid, block, 0, s, a);            \
-            }                                                                               \
-        } else if (a.pooled) hipLaunchKernelGGL((srd_roll16_kernel<P, true>), grid, block, 0, s, a);  \
-        else hipLaunchKernelGGL((srd_roll16_kernel<P, false>), grid, block, 0, s, a);          \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3: DFFW_SRD16_LAUNCH(P_BF16X3); break;
-        case P_FP16: DFFW_SRD16_LAUNCH(P_FP16); break;
-        case P_BF16: DFFW_SRD16_LAUNCH(P_BF16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_SRD16_LAUNCH
-#undef DFFW_SRD16_ABL_CASES
-    return hipGetLastError();
+    return launch_row(select_srd_roll16(prec, a.pooled != nullptr), a.total_tiles, a.wgs > 0 ? a.wgs : 512, 1, s, a);   // 512: two resident workgroups per CU
 }
 
-hipError_t launch_srd_roll(int prec, const SrdArgs &a, hipStream_t s) {
-    const int want = a.wgs > 0 ? a.wgs : 768;   // three resident workgroups per CU
-    const int per_xcd = (a.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(256);
-#ifdef DFFW_ABL_BUILD   // development (make ABL=1): timing ablations, selected with DFFW_SRD_ABL (wrong results with any bit set)
-    const char *az = getenv("DFFW_SRD_ABL");
-    const int abl = az ? atoi(az) : 0;
-#define DFFW_SRD_ABL_CASES \
-    case 1: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 1>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 2: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 2>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 4: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 4>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 6: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 6>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 7: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 7>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 8: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 8>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 16: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 16>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 32: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 32>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 40: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 40>), grid, block, 0, s, a, a.w3, a.w1); break; \
-    case 23: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true, 23>), grid, block, 0, s, a, a.w3, a.w1); break; \
-
-#else
-    const int abl = 0;
-#define DFFW_SRD_ABL_CASES
-#endif
-#define DFFW_SRD_LAUNCH(P)                                                                    \
-    do {                                                                                      \
-        if (a.pooled && P == P_BF16X3 && abl) {                                               \
-            switch (abl) {                                                                    \
-                DFFW_SRD_ABL_CASES                                                            \
-                default: hipLaunchKernelGGL((srd_roll_kernel<P_BF16X3, true>), grid, block, 0, s, a, a.w3, a.w1);            \
-            }                                                                                 \
-        } else if (a.pooled) hipLaunchKernelGGL((srd_roll_kernel<P, true>), grid, block, 0, s, a, a.w3, a.w1);   \
-        else hipLaunchKernelGGL((srd_roll_kernel<P, false>), grid, block, 0, s, a, a.w3, a.w1);           \
-    } while (0)
-    switch (prec) {
-        case P_BF16X3: DFFW_SRD_LAUNCH(P_BF16X3); break;
-        case P_FP16: DFFW_SRD_LAUNCH(P_FP16); break;
-        case P_BF16: DFFW_SRD_LAUNCH(P_BF16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef DFFW_SRD_LAUNCH
-#undef DFFW_SRD_ABL_CASES
-    return hipGetLastError();
+static const SrdRow kSrdPipe16[] = {   // [prec][plain | pooled]
+#define R(...) DFFW_ROW(256, srd_pipe16_kernel, __VA_ARGS__)
+    R(0, false, 0), R(0, true, 0), R(1, false, 0), R(1, true, 0), R(2, false, 0), R(2, true, 0),
+#undef R
+};
+void srd_pipe16_kernel_name(int prec, bool pool, char *buf, int n) { copy_row_name(prec_row(kSrdPipe16, prec, 2, pool), buf, n); }
+hipError_t launch_srd_pipe16(int prec, const SrdArgs &a, hipStream_t s) {
+    return launch_row(prec_row(kSrdPipe16, prec, 2, a.pooled != nullptr), a.total_tiles, a.wgs > 0 ? a.wgs : 512, 1, s, a);   // 512: two resident workgroups per CU
 }
+#undef DFFW_SRD_ROWS
 
 }  // namespace dffw

@@ -18,6 +18,7 @@
 
 #include "dffw_conv_geom.h"
 #include "dffw_device.h"
+#include "dffw_persist.h"
 #include "dffw_stem.h"
 
 namespace dffw {
@@ -48,14 +49,8 @@ __global__ __launch_bounds__(512) void stem_pipe(const ConvArgs a, const TileArg
 
     // ---- this workgroup's tiles: XCD x (= blockIdx % 8) owns a contiguous range of the tile sequence (x fastest, then y, slice, sample)
     // and its workgroups take them round-robin ----
-    const int xcd = blockIdx.x & 7, widx = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-    int tfirst, tend;
-    {
-        const int q = t.total_tiles >> 3, rem = t.total_tiles & 7;
-        const int xs = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-        tend = xs + q + (xcd < rem ? 1 : 0);
-        tfirst = xs + widx;
-    }
+    const UnitRange ur = persistent_range(t.total_tiles);   // dffw_persist.h
+    const int tfirst = ur.first, tend = ur.end, wgs_per_xcd = ur.step;
     if (tfirst >= tend) return;
     struct Coord {
         int b, gz0, gy0, gx0;
@@ -245,15 +240,10 @@ bool stem_pipe_ok(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArg
            a.Cout == 8 && a.Hg % stemp::TY == 0 && a.Wg % stemp::TX == 0 && t.nsplit == 1 && t.ksplit <= 1 && !a.trace && (a.Wi - 2) % 4 == 0;
 }
 
+static const KernelRow<ConvArgs, TileArgs> kStemPipe[] = {DFFW_ROW(stemp::NW * 64, stem_pipe, false), DFFW_ROW(stemp::NW * 64, stem_pipe, true)};   // [relu]
 hipError_t launch_stem_pipe(const ConvArgs &a, const TileArgs &t, int wgs, hipStream_t s) {
-    const int want = wgs > 0 ? wgs : 512;   // two resident workgroups per CU
-    const int per_xcd = (t.total_tiles + 7) / 8;
-    const dim3 grid((unsigned)(8 * std::min(per_xcd, std::max(1, want / 8)))), block(stemp::NW * 64);
-    if (a.relu == 1) hipLaunchKernelGGL((stem_pipe<true>), grid, block, 0, s, a, t);
-    else hipLaunchKernelGGL((stem_pipe<false>), grid, block, 0, s, a, t);
-    return hipGetLastError();
+    return launch_row(&kStemPipe[a.relu == 1], t.total_tiles, wgs > 0 ? wgs : 512, 1, s, a, t);   // 512: two resident workgroups per CU
 }
-
-void stem_pipe_kernel_name(const ConvArgs &a, char *buf, int n) { snprintf(buf, n, "dffw::stem_pipe<%s>", a.relu == 1 ? "true" : "false"); }
+void stem_pipe_kernel_name(const ConvArgs &a, char *buf, int n) { copy_row_name(&kStemPipe[a.relu == 1], buf, n); }
 
 }  // namespace dffw

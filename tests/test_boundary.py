@@ -185,3 +185,43 @@ def test_isa_wait_lint_finds_the_round6_hazard_and_nothing_else():
         roll = subprocess.run([sys.executable, tool, os.path.join(root, "dffinthewild_amd", "csrc", name)], capture_output=True, text=True)
         print(roll.stdout)
         assert roll.returncode == 0 and "HAZARD" not in roll.stdout and name in roll.stdout, roll.stdout
+
+
+# the PINNED names that are a shortened spelling of the kernel symbols they stand for (labels, kept because the dispatch pins and the profile tools were
+# recorded with them).  This guards the pin file only: the launch tables hold further hand-written labels that no pinned case reports (of_roll_kernel<P, CIN8>,
+# the other srd_roll / srd_roll16 / conv_rollx_pair rows), and the test does not reach those.  A new instantiation reports its symbol (one DFFW_ROW in its
+# family's table), so this map does not grow.
+SHORT_NAMES = {
+    "dffw::srd_roll_kernel<0, true>": ["dffw::srd_roll_kernel<0, true, 0>"],
+    "dffw::srd_roll16_kernel<0, true>": ["dffw::srd_roll16_kernel<0, true, 0>"],
+    "dffw::conv_rollx_pair<true>": ["dffw::conv_rollx_pair<true, 0, false>"],
+    "dffw::regress_fused_kernel": ["dffw::regress_fused_kernel<10>", "dffw::regress_fused_kernel<16>"],
+    "dffw::splitk_finish_kernel": ["dffw::splitk_finish_kernel<0>", "dffw::splitk_finish_kernel<1>", "dffw::splitk_finish_kernel<2>"],
+}
+
+
+def test_every_pinned_kernel_name_is_a_kernel_of_the_library(lib_built, tmp_path):
+    """What a launch reports (Engine.last_conv_kernel(), the launch lines of tests/data/dispatch_pins.json, the names tools/ match against rocprofv3) is the
+    demangled symbol of a gfx950 kernel in libdffw.so's code objects, or one of the five shortened spellings above, whose symbols all exist."""
+    import json
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import isa_compare as ic
+    finally:
+        sys.path.pop(0)
+    mangled = []
+    for co in ic.code_objects(lib_built, str(tmp_path)):
+        mangled += list(ic.kernel_notes(co))
+    demangled = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.splitlines()
+    symbols = {re.sub(r"\(.*", "", d).replace("void ", "", 1) for d in demangled}   # return type and argument list stripped
+    assert len(symbols) > 400 and all(s.startswith("dffw::") for s in symbols), len(symbols)
+    pins = json.load(open(os.path.join(ROOT, "tests", "data", "dispatch_pins.json")))
+    names = {line.split("\t")[0] for case in pins.values() for line in case.get("lines", [])}
+    assert len(names) > 50, len(names)
+    assert len(SHORT_NAMES) == 5
+    for short, stands_for in SHORT_NAMES.items():
+        assert short not in symbols and stands_for and all(s in symbols for s in stands_for), (short, stands_for)
+    unknown = sorted(n for n in names if n not in symbols and n not in SHORT_NAMES)
+    assert not unknown, unknown

@@ -269,27 +269,35 @@ def _profiled_kernels(model, *inputs):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16", "bf16"])
-@pytest.mark.parametrize("B,H,W", [(1, 256, 256), (3, 96, 224), (4, 256, 256)])
+@pytest.mark.parametrize("B,H,W", [(1, 256, 256), (3, 96, 224), (4, 256, 256), (1, 32, 32), (3, 32, 96)])
 def test_hip_e2e_head_warp_streaming_kernel(lib_built, monkeypatch, B, H, W, precision):
     """head_warp_kernel (dffw_align.hip): the level-1 (8-channel, full resolution) and, on large enough batches, level-2 (16-channel,
     half resolution) heads' first conv over [warp(fe) | flow] with the bilinear gather done one slice ahead while staging
     (End_to_End.py:88-101 without the warped volume) against flow_volume + conv_tile (DFFW_NO_HEAD_WARP):
     magnifying, shrinking and out-of-image warps, columns on every image border; the profile proves which kernel ran; default
-    arithmetic also against the oracle."""
+    arithmetic also against the oracle.  The two 32-row images (the smallest the network takes, forced onto the kernel with DFFW_ROLL_MIN_UNITS=1) are
+    the walk's edge cases: 1 x 32 x 32 = 8 columns at level 1 (one per XCD) and 2 at level 2 (six XCDs idle); 3 x 32 x 96 on 8 workgroups = 72 columns at
+    level 1 and 18 at level 2 (a remainder of 2 over the XCDs, each workgroup walking its XCD's whole range)."""
     g, sd, FS, fd, fov = load(GOLDEN[0])
     from dffinthewild_amd import synth
+    small = H == 32
+    if small:
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")          # (the conv_tile partner below would otherwise be conv_small)
+        if B == 3:
+            monkeypatch.setenv("DFFW_SRD_WGS", "8")
     FS = torch.from_numpy(synth.focal_stack(B, 10, H, W, seed=29))
     fd = fd[:1].expand(B, -1, -1, -1).contiguous()
     fov = torch.cat([1.0 + (fov[:1] - 1.0) * k for k in (1.0, -2.5, 4.0, 0.3)][:B], 0).contiguous()
     tags = ["head3", "head2", "head1", "alpha"]
-    if B == 3:
+    if B == 3 and not small:
         monkeypatch.setenv("DFFW_SRD_WGS", "16")         # two workgroups per XCD: every workgroup walks a long stream of columns
     m = _model(sd, precision)
     with torch.no_grad():
         outs, taps = m.forward_with_taps(FS.cuda(), fd.cuda(), fov.cuda(), tags)
     ran = [k for k, layer in _profiled_kernels(m, FS.cuda(), fd.cuda(), fov.cuda()) if layer.endswith(".0.0#cur")]
     assert len(ran) == 3 and ran[2].startswith("dffw::head_warp_kernel<%d, 8>" % PREC_ID[precision]), ran
-    level2 = B * (H // 16) * (W // 32) >= 256 and (H // 2) % 8 == 0 and (W // 2) % 16 == 0
+    level2 = B * (H // 16) * (W // 32) >= (1 if small else 256) and (H // 2) % 8 == 0 and (W // 2) % 16 == 0
     assert ran[1].startswith("dffw::head_warp_kernel<%d, 16>" % PREC_ID[precision]) == level2, ran
     monkeypatch.setenv("DFFW_NO_HEAD_WARP", "1")
     m2 = _model(sd, precision)

@@ -103,7 +103,9 @@ def of_expected(block, H, W, path, pi):
 # (B, N, H, W, wgs) of the block's input: slice counts 1, 2, 3, 10, batch up to 4, one column per workgroup and long column streams
 # (DFFW_SRD_WGS 8 / 16), and sizes that miss the streaming forms: W % 16 (24 x 40), H % 8 (20 x 32), and of_s2's W % 32 only (16 x 48)
 OF_SHAPES = [(1, 10, 32, 64, 0), (2, 1, 16, 32, 8), (4, 3, 16, 32, 16), (1, 2, 32, 96, 0), (2, 3, 24, 40, 0), (1, 2, 20, 32, 8),
-             (3, 1, 16, 48, 8)]
+             (3, 1, 16, 48, 8),
+             # fewer columns than XCDs at stride 1 (4; of_s2: 1), and of_s2's own remainder on 8 workgroups (3 x 3 = 9 output columns; stride 1: 36)
+             (1, 2, 16, 32, 0), (3, 1, 16, 96, 8)]
 
 
 def _of_case(block, shape, prec):

@@ -77,8 +77,8 @@ def _set(monkeypatch, env):
 # ---- SRD, 8 and 16 channels --------------------------------------------------------------------------------------------------
 # (B, N, H, W, wgs): realistic V1 / V2 tiles (8 x 16 and 4 x 16 columns), slice counts 1, 2, 3, 10, 15, non-square maps, batch up to
 # 4, one column per workgroup and long column streams, column counts that are not a multiple of 8 (2 x 4 x 3 = 24 / 2 x 8 x 3 = 48
-# columns of 8 x 16; 3 x 4 x 5 = 60 of 4 x 16)
-SRD_SHAPES = [(1, 10, 64, 128, 0), (2, 1, 32, 48, 8), (4, 3, 16, 32, 16), (1, 2, 32, 64, 0), (2, 15, 16, 32, 8), (3, 3, 16, 80, 16)]
+# columns of 8 x 16; 3 x 4 x 5 = 60 of 4 x 16), fewer columns than XCDs (3 x 2 = 6 of 8 x 16 / of 4 x 16: two XCDs' workgroups have nothing to do)
+SRD_SHAPES = [(1, 10, 64, 128, 0), (2, 1, 32, 48, 8), (4, 3, 16, 32, 16), (1, 2, 32, 64, 0), (2, 15, 16, 32, 8), (3, 3, 16, 80, 16), (3, 2, 16, 16, 0)]
 
 
 def srd_paths(C):

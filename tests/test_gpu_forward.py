@@ -450,14 +450,29 @@ def test_config3_batch32_two_goldens_and_properties(lib_built, monkeypatch):
 def test_lean_epilogue_and_merged_heads_are_bit_identical(lib_built, which, monkeypatch):
     """conv_tile's LEAN instantiations (straight-line epilogue) run the same arithmetic in the same order as the generic
     epilogue_quad, the four regression heads in one launch the same as one launch each, and the few-tile launches' weight warm-up
-    (TileArgs::warm) only touches memory: all four outputs bit for bit."""
+    (TileArgs::warm) only touches memory: all four outputs bit for bit.  So is the persistent stem (stem_pipe, which the profile shows serving the stem by
+    default) against conv_tile's pair form (DFFW_NO_STEM_PIPE), and on 8 workgroups (DFFW_ROLL_WGS=8): its 32 x 32 x 1-slice tiles number 1 (one_slice: seven
+    XCDs idle), 30, 60, 245 (ddff_5x224: a remainder of 5 over the XCDs; on 8 workgroups each walks its XCD's 30 or 31 tiles) and 640."""
     path = [p for p in GOLDEN if which in p][0]
     g, meta, FS, fd, sd = case(path)
     model = model_for(sd, (meta["wseed"], meta["profile"]))
+    engine = model._engine_on(FS.cuda().device)
+
+    def stem_kernel():
+        engine.profile(True)
+        model(FS.cuda(), fd.cuda())
+        rows = engine.profile_collect()
+        engine.profile(False)
+        ks = [r[0] for r in rows if r[1] == "DFF_net.FM_measure.Focus_extraction.0.0"]
+        assert len(ks) == 1, rows
+        return ks[0]
     with torch.no_grad():
         base = [o.clone() for o in model(FS.cuda(), fd.cuda())]
-        for env, val in (("DFFW_NO_LEAN_TILE", "1"), ("DFFW_NO_LEAN_ROLL", "1"), ("DFFW_NO_REGRESS_FUSED", "1"), ("DFFW_NO_STEM_PIPE", "1"), ("DFFW_NO_POOL3", "1"), ("DFFW_WARM_MAX_WGS", "0")):
+        assert stem_kernel() == "dffw::stem_pipe<true>"
+        for env, val in (("DFFW_NO_LEAN_TILE", "1"), ("DFFW_NO_LEAN_ROLL", "1"), ("DFFW_NO_REGRESS_FUSED", "1"), ("DFFW_NO_STEM_PIPE", "1"), ("DFFW_NO_POOL3", "1"), ("DFFW_WARM_MAX_WGS", "0"),
+                         ("DFFW_ROLL_WGS", "8")):
             monkeypatch.setenv(env, val)
+            assert stem_kernel().startswith("dffw::conv_tile<" if env == "DFFW_NO_STEM_PIPE" else "dffw::stem_pipe<"), env
             alt = model(FS.cuda(), fd.cuda())
             torch.cuda.synchronize()
             monkeypatch.delenv(env)

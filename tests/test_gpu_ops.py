@@ -138,7 +138,10 @@ def test_conv_families(eng, case, prec):
 @pytest.mark.parametrize("cin,cout,B,N,H,W,relu,wgs", [(16, 32, 2, 10, 128, 128, 1, 0), (16, 32, 4, 1, 128, 64, 0, 16), (16, 32, 2, 2, 128, 128, 1, 40),
                                                        (16, 16, 4, 10, 128, 128, 1, 0), (16, 16, 4, 3, 256, 64, 0, 24), (16, 16, 8, 1, 64, 128, 1, 8),
                                                        (32, 32, 2, 10, 128, 128, 1, 0), (32, 32, 4, 1, 128, 64, 0, 16), (32, 32, 2, 3, 128, 128, 0, 40),
-                                                       (32, 64, 2, 10, 128, 128, 1, 0), (32, 64, 8, 2, 64, 128, 0, 24)])
+                                                       (32, 64, 2, 10, 128, 128, 1, 0), (32, 64, 8, 2, 64, 128, 0, 24),
+                                                       # 3 and 9 columns of the family's smallest grid (4 x 8 / 4 x 16 / 4 x 8 output pixels), the 9 on 8 workgroups
+                                                       (16, 32, 3, 3, 8, 16, 1, 0), (16, 32, 9, 2, 8, 16, 0, 8), (16, 16, 3, 3, 8, 32, 1, 0), (16, 16, 9, 2, 8, 32, 0, 8),
+                                                       (32, 32, 3, 3, 8, 16, 1, 0), (32, 32, 9, 2, 8, 16, 0, 8)])
 def test_conv_roll_strided_16_channels(eng, cin, cout, B, N, H, W, relu, wgs, prec, monkeypatch):
     """conv_roll_s2 (dffw_conv_roll.hip): 3x3x3 stride (1,2,2) as a rolling window over whole pixel records.  16 input channels
     (`FM_conv2.0.stride_conv`, `dres3.conv1`: 16 -> 32; `dres4.conv3`: 16 -> 16; DEN.py:306-315, 252-256) and 32 with the
@@ -151,6 +154,9 @@ def test_conv_roll_strided_16_channels(eng, cin, cout, B, N, H, W, relu, wgs, pr
     ref = ref_bn(F.conv3d(x, w, None, (1, 2, 2), 1), bn)
     if relu:
         ref = F.relu(ref)
+    if H == 8:   # the few-column cases (3 units: some XCDs idle; 9: a remainder over the 8 XCDs, walked by 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     got = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=relu, precision=prec)
@@ -309,7 +315,9 @@ def test_conv_tile_teams_transposed(eng, cin, cout, B, N, H, W, residual, kt, pr
 @pytest.mark.parametrize("cout,N,H,W,zsplit,residual,wgs", [(8, 10, 128, 128, 1, True, 0), (16, 5, 128, 128, 1, False, 24), (8, 1, 64, 256, 1, False, 8),
                                                              (16, 10, 64, 256, 2, True, 40), (16, 7, 128, 128, 3, False, 0), (8, 2, 128, 128, 2, True, 16),
                                                              (8, 10, 128, 128, 1, False, 0), (8, 7, 64, 256, 3, False, 24), (8, 2, 128, 128, 2, False, 16),
-                                                             (8, 3, 128, 128, 3, False, 8)])
+                                                             (8, 3, 128, 128, 3, False, 8),
+                                                             # 3 and 5 columns of 8 x 16 per sample = 6 and 10 units, the 10 on 8 workgroups
+                                                             (16, 3, 8, 48, 1, False, 0), (16, 3, 8, 80, 1, True, 8), (8, 3, 8, 48, 1, False, 0), (8, 3, 8, 80, 1, False, 8)])
 def test_conv_roll_rolling_window(eng, cout, N, H, W, zsplit, residual, wgs, prec, monkeypatch):
     """conv_roll (dffw_conv_roll.hip): the 16-channel 3x3x3 stride-1 layers of the full-resolution hourglass
     (DEN.py:240-284, dres4.conv0 / conv2) as a rolling window along the slices; every slice count incl. 1 and 2,
@@ -324,6 +332,9 @@ def test_conv_roll_rolling_window(eng, cout, N, H, W, zsplit, residual, wgs, pre
     ref = ref_bn(F.conv3d(x, w, None, 1, 1), bn)
     ref = F.relu(ref + res) if residual else F.relu(ref)
     monkeypatch.setenv("DFFW_ROLL_ZSPLIT", str(zsplit))
+    if H == 8:   # the few-column cases (6 units: some XCDs idle; 10: a remainder over the 8 XCDs, walked by 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     got = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, residual=res.cuda() if residual else None, relu=1, precision=prec)
@@ -349,7 +360,8 @@ def test_conv_roll_rolling_window(eng, cout, N, H, W, zsplit, residual, wgs, pre
 
 
 @pytest.mark.parametrize("N,H,W,zsplit,wgs,relu", [(10, 128, 128, 1, 0, 1), (1, 64, 256, 1, 8, 1), (7, 64, 256, 3, 24, 0), (2, 128, 128, 2, 16, 1), (3, 128, 128, 3, 8, 1),
-                                                    (5, 256, 64, 1, 0, 1)])
+                                                    (5, 256, 64, 1, 0, 1),
+                                                    (3, 8, 48, 1, 0, 1), (3, 8, 80, 1, 8, 0)])   # 6 and 10 units (3 / 5 columns of 8 x 16 per sample), the 10 on 8 workgroups
 def test_conv_rollx_k2(eng, N, H, W, zsplit, wgs, relu, monkeypatch):
     """conv_rollx_k2 (dffw_conv_rollx.hip): 3x3x3 stride 1, 32 -> 16 channels (`dres3.conv0`, DEN.py:240-284) as a software-pipelined rolling
     window with the contraction split over the two 16-channel input halves (8 waves, partial tiles exchanged through LDS): every slice count
@@ -363,6 +375,9 @@ def test_conv_rollx_k2(eng, N, H, W, zsplit, wgs, relu, monkeypatch):
     if relu:
         ref = F.relu(ref)
     monkeypatch.setenv("DFFW_ROLL_ZSPLIT", str(zsplit))
+    if H == 8:   # the few-column cases (6 units: some XCDs idle; 10: a remainder over the 8 XCDs, walked by 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     got = eng.op_conv3d(x.cuda(), w, pad=1, bn=bn, relu=relu, precision="bf16x3")
@@ -592,7 +607,8 @@ def test_conv_rollt_second_output_and_classifier(eng, cin, cout, N, H, W, wgs, r
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
 @pytest.mark.parametrize("N,H,W,zsplit,residual,wgs", [(10, 64, 256, 1, True, 0), (5, 128, 128, 1, False, 16), (1, 64, 256, 1, True, 8),
-                                                        (7, 64, 256, 3, False, 24), (2, 128, 128, 2, True, 0)])
+                                                        (7, 64, 256, 3, False, 24), (2, 128, 128, 2, True, 0),
+                                                        (3, 8, 48, 1, True, 0), (3, 8, 80, 1, False, 8)])   # 6 and 10 units (3 / 5 input columns of 8 x 16 per sample), the 10 on 8 workgroups
 def test_conv_roll_transposed(eng, N, H, W, zsplit, residual, wgs, prec, monkeypatch):
     """conv_roll_t: ConvTranspose3d k3 s(1,2,2) p1 op(0,1,1), 16 -> 8 channels (`deconv_3`, `dres4.conv6`, DEN.py:41-48) as a
     rolling window over the input slices with the two x phases of an input column in the two halves of the result tile;
@@ -606,6 +622,9 @@ def test_conv_roll_transposed(eng, N, H, W, zsplit, residual, wgs, prec, monkeyp
     ref = ref_bn(F.conv_transpose3d(x, w, None, (1, 2, 2), 1, (0, 1, 1)), bn)
     ref = F.relu(ref + res) if residual else F.relu(ref)
     monkeypatch.setenv("DFFW_ROLL_ZSPLIT", str(zsplit))
+    if H == 8:   # the few-column cases (6 units: some XCDs idle; 10: a remainder over the 8 XCDs, walked by 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     kw = dict(transposed=True, stride=(1, 2, 2), pad=1, bn=bn, residual=res.cuda() if residual else None, relu=1, precision=prec)
@@ -648,7 +667,8 @@ def test_no_lean_roll_switch_reaches_every_rolling_kernel(eng, monkeypatch):
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
 @pytest.mark.parametrize("cin", [32, 16])
-@pytest.mark.parametrize("N,H,W,residual,wgs", [(10, 64, 256, True, 0), (1, 128, 128, False, 8), (2, 64, 256, True, 16), (5, 128, 128, False, 24)])
+@pytest.mark.parametrize("N,H,W,residual,wgs", [(10, 64, 256, True, 0), (1, 128, 128, False, 8), (2, 64, 256, True, 16), (5, 128, 128, False, 24),
+                                                (3, 8, 48, True, 0), (3, 8, 80, False, 8)])   # 6 / 12 and 10 / 20 units (even / odd row sweep), the latter on 8 workgroups
 def test_conv_roll_transposed_32(eng, N, H, W, residual, wgs, cin, prec, monkeypatch):
     """conv_roll_t32: ConvTranspose3d k3 s(1,2,2) p1 op(0,1,1), 32 -> 16 channels (`deconv_2`, `dres3.conv6`, DEN.py:41-48) as two
     rolling sweeps, one per output row phase (each with only that phase's taps resident); + BN + residual + ReLU.  cin = 16
@@ -660,6 +680,9 @@ def test_conv_roll_transposed_32(eng, N, H, W, residual, wgs, cin, prec, monkeyp
     res = rnd(B, cout, N, 2 * H, 2 * W, seed=54) if residual else None
     ref = ref_bn(F.conv_transpose3d(x, w, None, (1, 2, 2), 1, (0, 1, 1)), bn)
     ref = F.relu(ref + res) if residual else F.relu(ref)
+    if H == 8:   # the few-column cases (6 / 12 units in the even / odd row sweep; 10 / 20 on 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     monkeypatch.setenv("DFFW_NO_ROLLT", "1")             # (round 6: in split-bf16 the 32 -> 16 layers run on conv_rollt's wide form; this is its fallback and the 16-input kernel)
@@ -678,7 +701,8 @@ def test_conv_roll_transposed_32(eng, N, H, W, residual, wgs, cin, prec, monkeyp
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
-@pytest.mark.parametrize("N,H,W,wgs", [(10, 128, 256, 0), (1, 128, 256, 8), (2, 256, 128, 16), (5, 64, 512, 24)])
+@pytest.mark.parametrize("N,H,W,wgs", [(10, 128, 256, 0), (1, 128, 256, 8), (2, 256, 128, 16), (5, 64, 512, 24),
+                                       (3, 8, 96, 0), (3, 8, 160, 8)])   # 6 and 10 units (3 / 5 columns of 4 x 16 output pixels per sample), the 10 on 8 workgroups
 def test_conv_roll_strided(eng, N, H, W, wgs, prec, monkeypatch):
     """conv_roll_efd<..., false>: 3x3x3 stride (1,2,2) 8 -> 16 channels (dres4.conv1, DEN.py:252) as a rolling window with
     the stride-2 footprint stored even columns first; vs F.conv3d and vs conv_tile on the same input."""
@@ -687,6 +711,9 @@ def test_conv_roll_strided(eng, N, H, W, wgs, prec, monkeypatch):
     w = rnd(cout, cin, 3, 3, 3, seed=42, scale=(2.0 / (cin * 27)) ** 0.5 * 1.7)
     bn = bn_params(cout, 43)
     ref = F.relu(ref_bn(F.conv3d(x, w, None, (1, 2, 2), 1), bn))
+    if H == 8:   # the few-column cases (6 units: some XCDs idle; 10: a remainder over the 8 XCDs, walked by 8 workgroups): below the default threshold, and their conv_tile partner would otherwise be conv_small
+        monkeypatch.setenv("DFFW_ROLL_MIN_UNITS", "1")
+        monkeypatch.setenv("DFFW_NO_SMALL", "1")
     if wgs:
         monkeypatch.setenv("DFFW_ROLL_WGS", str(wgs))
     got = eng.op_conv3d(x.cuda(), w, stride=(1, 2, 2), pad=1, bn=bn, relu=1, precision=prec)

@@ -1,5 +1,5 @@
 """Are the gfx950 kernels of two builds of csrc/ the same machine code?  For a change that only moves kernels between source files.
-usage: python tools/isa_compare.py PARENT_CSRC HEAD_CSRC [object whose kernels are listed one by one, default dffw_srd_roll.o]
+usage: python tools/isa_compare.py PARENT_CSRC HEAD_CSRC [objects whose kernels are listed one by one, or `all`; default dffw_srd_roll.o]
 
 Both directories hold a finished `make` (objects + ../libdffw.so).  Per kernel of the parent's object: the kernel of the same name in
 the head's objects, its instruction stream (llvm-objdump -d without addresses, encodings and symbol offsets) and its resource notes
@@ -38,15 +38,22 @@ def code_objects(path, tmp):
     return out
 
 
+def kernel_notes(co):
+    """{mangled kernel name: {note: value}} of one code object (the entries of its metadata that carry an argument list: an argument's own
+    `.name:` is not a kernel)"""
+    notes = {}
+    for block in re.split(r"\n  - (?=\.)", run(LLVM + "llvm-readelf", "--notes", co)):
+        name = re.search(r"^\s*\.name:\s+(\S+)", block, re.M)
+        if name and ".args:" in block:
+            notes[name.group(1)] = {k: (re.search(r"^\s*%s:\s+(\S+)" % re.escape(k), block, re.M) or [0, "0"])[1] for k in NOTES}
+    return notes
+
+
 def kernels(path, tmp):
     """{mangled kernel name: (instruction lines, {note: value})} of one object or library"""
     res = {}
     for co in code_objects(path, tmp):
-        notes = {}
-        for block in re.split(r"\n  - (?=\.)", run(LLVM + "llvm-readelf", "--notes", co)):
-            name = re.search(r"^\s*\.name:\s+(\S+)", block, re.M)
-            if name and ".args:" in block:
-                notes[name.group(1)] = {k: (re.search(r"^\s*%s:\s+(\S+)" % re.escape(k), block, re.M) or [0, "0"])[1] for k in NOTES}
+        notes = kernel_notes(co)
         cur = None
         for line in run(LLVM + "llvm-objdump", "-d", co).splitlines():
             m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
@@ -59,24 +66,30 @@ def kernels(path, tmp):
 
 def main():
     parent, head = sys.argv[1], sys.argv[2]
-    listed = sys.argv[3] if len(sys.argv) > 3 else "dffw_srd_roll.o"
+    listed = sys.argv[3:] or ["dffw_srd_roll.o"]
+    if listed == ["all"]:
+        listed = sorted(os.path.basename(o) for o in glob.glob(os.path.join(parent, "*.o")))
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
-        old = kernels(os.path.join(parent, listed), tmp)
+        old = {}
+        for o in listed:
+            old.update(kernels(os.path.join(parent, o), tmp))
         new = {}
         for o in sorted(glob.glob(os.path.join(head, "*.o"))):
             for k, v in kernels(o, tmp).items():
                 new[k] = v + (os.path.basename(o),)
-        print("kernels of the parent's %s against the kernel of the same name in the head's objects (gfx950)" % listed)
+        print("kernels of the parent's %s against the kernel of the same name in the head's objects (gfx950)" % " ".join(listed))
         print("%-62s %6s %4s %4s %4s %6s %7s %6s  %-16s %s" % ("kernel", "insns", "VGPR", "AGPR", "SGPR", "LDS", "scratch", "spills", "head object", ""))
-        for k in sorted(old, key=lambda k: run("c++filt", k)):
+        names = {k: run("c++filt", k).strip() for k in old}
+        for k in sorted(old, key=names.get):
             ins, nt = old[k]
-            name = re.sub(r"\(.*", "", run("c++filt", k).strip()).replace("void dffw::", "")
+            name = re.sub(r"\(.*", "", names[k]).replace("void dffw::", "")
             h = new.get(k)
             same = h is not None and h[0] == ins and h[1] == nt
             bad += not same
             print("%-62s %6d %4s %4s %4s %6s %7s %6s  %-16s %s" % (name, len(ins), nt[NOTES[0]], nt[NOTES[1]], nt[NOTES[2]], nt[NOTES[3]], nt[NOTES[4]],
                                                               nt[NOTES[5]] + "/" + nt[NOTES[6]], h[2] if h else "-", "same" if same else "differs" if h else "MISSING"))
+        print("%d kernels listed, %d not the same" % (len(old), bad))
         lib_old, lib_new = (set(kernels(os.path.join(d, "..", "libdffw.so"), tmp)) for d in (parent, head))
         print("\nkernel symbols in libdffw.so: parent %d, head %d, only in parent %s, only in head %s" % (len(lib_old), len(lib_new), sorted(lib_old - lib_new), sorted(lib_new - lib_old)))
         bad += lib_old != lib_new

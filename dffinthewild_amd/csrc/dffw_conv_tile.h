@@ -45,7 +45,8 @@ struct TileCfg {
     int fz, fy, fx, fxl;
     int pipe;            // 1: software-pipelined MFMA loop (compute-bound layers), 0: lean loop (bandwidth-bound)
     int nw;              // waves per workgroup (4, or 8 for the wide tiles) -- per TEAM for the team configurations
-    int kt = 1;          // teams per workgroup (> 1: the contraction depth split inside the workgroup, see conv_tile's header; nw * kt waves)
+    int kt;              // teams per workgroup (> 1: the contraction depth split inside the workgroup, see conv_tile's header; nw * kt waves)
+    bool lean;           // a launch the LEAN instantiation covers takes it (false: it costs this configuration registers, see DFFW_TILE_IDS_NO_LEAN)
 };
 
 struct TileArgs {
@@ -66,6 +67,11 @@ struct TileArgs {
     int warm;                 // few-tile launches on cold weights: every workgroup first touches the weight lines of its whole contraction walk
 };
 
+// The instantiations of a configuration.  PLAIN: the generic epilogue; LEAN: the straight-line one (split-bf16 only); the other three are the kernel's
+// SPLITK = true: fp32 partial sums of a stage range (TileArgs::ksplit > 1), the stem on a raw stack (DFFW_ARGS_RAW), row sums (DFFW_ARGS_SUMS)
+enum class TileVariant { PLAIN, LEAN, SPLITK, RAW, SUMS };
+constexpr int TILE_VARIANTS = 5;
+
 // returns nullptr when no instantiation covers (geo, nt, cg)
 // wide: prefer an 8-wave 640-point instantiation when one exists
 const TileCfg *tile_cfg_find(int geo, int nt, int cg, bool wide = false);
@@ -76,12 +82,12 @@ const TileCfg *tile_cfg_find_like(const TileCfg *base, int nt);
 // the team configuration that replaces a split-K launch of `base` (same pack) over `nstage` stages -- one stage per team -- with `nt` output tiles per
 // workgroup, or nullptr
 const TileCfg *tile_cfg_find_team(const TileCfg *base, int nstage, int nt);
-bool tile_cfg_has_splitk(const TileCfg *c);   // a split-K instantiation of this configuration exists
-bool tile_cfg_has_sums(const TileCfg *c);     // a row-sums instantiation (DFFW_ARGS_SUMS: per-row sums through ConvArgs::outf, nothing stored) exists
+bool tile_cfg_has_splitk(const TileCfg *c);   // the SPLITK row of this configuration exists
+bool tile_cfg_has_sums(const TileCfg *c);     // the SUMS row (DFFW_ARGS_SUMS: per-row sums through ConvArgs::outf, nothing stored) exists
 int tile_cfg_count();
 const TileCfg *tile_cfg_at(int i);
+// the launch and the name it reports read the same row of the instantiation table (select_tile(), dffw_conv_tile.hip); no row: hipErrorInvalidValue / ""
 hipError_t launch_conv_tile(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s);
-bool tile_lean(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArgs &t);   // the launch runs the LEAN instantiation (straight-line epilogue)
-void conv_tile_kernel_name(int prec, const TileCfg *cfg, bool splitk, bool lean, char *buf, int n);
+void conv_tile_kernel_name(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, char *buf, int n);
 
 }  // namespace dffw

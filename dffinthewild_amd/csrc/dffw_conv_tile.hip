@@ -19,6 +19,7 @@
 // contiguous range of tiles so neighbouring tiles' halos hit in that XCD's L2.
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "dffw_conv_geom.h"
 
@@ -33,7 +34,7 @@ namespace dffw {
 // SPLITK: the split-K variant (raw fp32 partial sums, stage range from blockIdx.z).  Compile-time because as a
 // runtime branch its partial-store path cost every kernel ~50 VGPRs at the peak (one resident wave per SIMD on the
 // 64-channel kernels); only the configurations that few-tile layers actually use are instantiated with it.
-// LEAN: the launch's epilogue is one the straight-line routine covers (tile_lean(): split-bf16 storage, out / out_pre / fused
+// LEAN: the launch's epilogue is one the straight-line routine covers (select_tile(): split-bf16 storage, out / out_pre / fused
 // classifier, at most one residual in the output's geometry, ReLU after it): epilogue_lean_t instead of epilogue_quad's run-time
 // option tree (which costs ~1000 cycles per operand tile and 16-channel group)
 // KT (round 6, "teams"): the split of the contraction depth INSIDE the workgroup -- KT teams of NWAVES waves, team z owns the channel-group stages
@@ -888,77 +889,64 @@ __global__ __launch_bounds__(NWAVES * KT * 64) void conv_tile(const ConvArgs a, 
 }
 
 // ---- configuration table -----------------------------------------------------------------------
-//        id  geo   NT  TZ TY  TX  CG
-#define DFFW_TILE_CONFIGS(X)         \
-    X(0, G3S1, 1, 5, 4, 16, 16, 1)   \
-    X(1, G3S1, 1, 5, 4, 16, 8, 1)    \
-    X(2, G3S1, 2, 5, 4, 16, 16, 1)   \
-    X(3, G3S1, 4, 5, 4, 16, 16, 1)   \
-    X(4, G3S1, 8, 4, 4, 8, 16, 1)    \
-    X(5, G3S2, 1, 5, 4, 16, 8, 1)    \
-    X(6, G3S2, 2, 5, 4, 16, 8, 1)    \
-    X(7, G3S2, 4, 5, 4, 16, 8, 1)    \
-    X(8, G3S2, 8, 4, 4, 8, 8, 1)     \
-    X(9, G3T, 1, 5, 4, 16, 16, 0)    \
-    X(10, G3T, 2, 5, 4, 16, 16, 1)   \
-    X(11, G3T, 4, 5, 4, 16, 16, 1)   \
-    X(12, G2S1, 1, 5, 4, 16, 8, 0)   \
-    X(13, G2S1, 1, 5, 4, 16, 16, 0)  \
-    X(14, G2S1, 2, 5, 8, 16, 16, 1)  \
-    X(15, G2D, 1, 1, 16, 32, 8, 0)   \
-    X(16, G3S1, 2, 4, 4, 8, 16, 1)   \
-    X(17, G3S2, 2, 4, 4, 8, 8, 1)    \
-    X(18, G2S1, 2, 5, 4, 16, 8, 1)   \
-    X(19, G2S1, 4, 5, 4, 16, 16, 1)  \
-    X(20, G2S1, 4, 5, 4, 16, 8, 1)   \
-    X(21, G2S2, 1, 5, 4, 16, 8, 0)   \
-    X(22, G2S2, 2, 5, 4, 16, 8, 0)   \
-    X(23, G3T, 1, 5, 4, 16, 32, 0)   \
-    X(24, G3T, 2, 5, 4, 16, 32, 1)   \
-    X(25, G3T, 4, 5, 4, 16, 32, 1)   \
-    X(34, G2S1, 2, 5, 4, 16, 32, 1)  \
-    X(37, G3S2, 4, 4, 4, 8, 16, 1)   \
-    X(38, G3S2, 2, 4, 4, 8, 16, 1)   \
-    X(39, G3S2, 1, 4, 4, 8, 16, 1)   \
-    X(32, G2P, 1, 1, 16, 32, 8, 0)   \
-    X(40, G3S1, 1, 5, 8, 8, 16, 1)   \
-    X(41, G3S1, 2, 5, 8, 8, 16, 1)   \
-    X(42, G3S1, 4, 5, 8, 8, 16, 1)   \
-    X(43, G3T, 1, 5, 8, 8, 32, 0)    \
-    X(44, G3T, 2, 5, 8, 8, 32, 1)    \
-    X(45, G3T, 4, 5, 8, 8, 32, 1)
+// One line per configuration; every other mention of a configuration below is its id.
+//        id  geo   NT  TZ TY  TX  CG  PIPE NW KT
+#define DFFW_TILE_CONFIGS(X)               \
+    X(0, G3S1, 1, 5, 4, 16, 16, 1, 4, 1)   \
+    X(1, G3S1, 1, 5, 4, 16, 8, 1, 4, 1)    \
+    X(2, G3S1, 2, 5, 4, 16, 16, 1, 4, 1)   \
+    X(3, G3S1, 4, 5, 4, 16, 16, 1, 4, 1)   \
+    X(4, G3S1, 8, 4, 4, 8, 16, 1, 4, 1)    \
+    X(5, G3S2, 1, 5, 4, 16, 8, 1, 4, 1)    \
+    X(6, G3S2, 2, 5, 4, 16, 8, 1, 4, 1)    \
+    X(7, G3S2, 4, 5, 4, 16, 8, 1, 4, 1)    \
+    X(8, G3S2, 8, 4, 4, 8, 8, 1, 4, 1)     \
+    X(9, G3T, 1, 5, 4, 16, 16, 0, 4, 1)    \
+    X(10, G3T, 2, 5, 4, 16, 16, 1, 4, 1)   \
+    X(11, G3T, 4, 5, 4, 16, 16, 1, 4, 1)   \
+    X(12, G2S1, 1, 5, 4, 16, 8, 0, 4, 1)   \
+    X(13, G2S1, 1, 5, 4, 16, 16, 0, 4, 1)  \
+    X(14, G2S1, 2, 5, 8, 16, 16, 1, 4, 1)  \
+    X(15, G2D, 1, 1, 16, 32, 8, 0, 4, 1)   \
+    X(16, G3S1, 2, 4, 4, 8, 16, 1, 4, 1)   \
+    X(17, G3S2, 2, 4, 4, 8, 8, 1, 4, 1)    \
+    X(18, G2S1, 2, 5, 4, 16, 8, 1, 4, 1)   \
+    X(19, G2S1, 4, 5, 4, 16, 16, 1, 4, 1)  \
+    X(20, G2S1, 4, 5, 4, 16, 8, 1, 4, 1)   \
+    X(21, G2S2, 1, 5, 4, 16, 8, 0, 4, 1)   \
+    X(22, G2S2, 2, 5, 4, 16, 8, 0, 4, 1)   \
+    X(23, G3T, 1, 5, 4, 16, 32, 0, 4, 1)   \
+    X(24, G3T, 2, 5, 4, 16, 32, 1, 4, 1)   \
+    X(25, G3T, 4, 5, 4, 16, 32, 1, 4, 1)   \
+    X(34, G2S1, 2, 5, 4, 16, 32, 1, 4, 1)  \
+    X(37, G3S2, 4, 4, 4, 8, 16, 1, 4, 1)   \
+    X(38, G3S2, 2, 4, 4, 8, 16, 1, 4, 1)   \
+    X(39, G3S2, 1, 4, 4, 8, 16, 1, 4, 1)   \
+    X(32, G2P, 1, 1, 16, 32, 8, 0, 4, 1)   \
+    X(40, G3S1, 1, 5, 8, 8, 16, 1, 4, 1)   \
+    X(41, G3S1, 2, 5, 8, 8, 16, 1, 4, 1)   \
+    X(42, G3S1, 4, 5, 8, 8, 16, 1, 4, 1)   \
+    X(43, G3T, 1, 5, 8, 8, 32, 0, 4, 1)    \
+    X(44, G3T, 2, 5, 8, 8, 32, 1, 4, 1)    \
+    X(45, G3T, 4, 5, 8, 8, 32, 1, 4, 1)
 // (40-45, round 4: 5 x 8 x 8 blocks for grids at most 8 wide -- the 1/32-resolution pyramid layers at 256 x 256: on the 5 x 4 x 16 block half of
 // every operand tile lies outside an 8 x 8 grid, and the 4 x 4 x 8 block re-streams the filter for 128 grid points at a time; tile_cfg_find_shape)
 // 8-wave "wide" variants: 640-point tiles, same work per wave.  Measured +8..17 % on the bandwidth-bound
 // single-stage layers with <= 16 output channels (one more resident wave per SIMD for the same LDS, 17 % less
 // halo per output), -10 % on the 32-channel / multi-stage ones, so the engine asks for them only for the former.
-#define DFFW_TILE_CONFIGS_W8(X)      \
-    X(26, G3S1, 1, 5, 8, 16, 16, 1)  \
-    X(27, G3T, 1, 5, 8, 16, 16, 0)   \
-    X(28, G2S1, 1, 5, 8, 16, 8, 0)   \
-    X(29, G2S1, 1, 5, 8, 16, 16, 0)  \
-    X(30, G2S1, 2, 5, 8, 16, 16, 0)  \
-    X(31, G2D, 1, 1, 32, 32, 8, 0)   \
-    X(33, G2P, 1, 1, 32, 32, 8, 0)
-
-// the 4-wave configurations few-tile layers end up on after the channel split (3x3x3 at stride 1 and 2, <= 32 output
-// channels per workgroup): these also exist as split-K kernels
-#define DFFW_TILE_CONFIGS_SPLITK(X)  \
-    X(0, G3S1, 1, 5, 4, 16, 16, 1)   \
-    X(1, G3S1, 1, 5, 4, 16, 8, 1)    \
-    X(2, G3S1, 2, 5, 4, 16, 16, 1)   \
-    X(16, G3S1, 2, 4, 4, 8, 16, 1)   \
-    X(5, G3S2, 1, 5, 4, 16, 8, 1)    \
-    X(6, G3S2, 2, 5, 4, 16, 8, 1)    \
-    X(17, G3S2, 2, 4, 4, 8, 8, 1)    \
-    X(38, G3S2, 2, 4, 4, 8, 16, 1)   \
-    X(39, G3S2, 1, 4, 4, 8, 16, 1)
+#define DFFW_TILE_CONFIGS_W8(X)            \
+    X(26, G3S1, 1, 5, 8, 16, 16, 1, 8, 1)  \
+    X(27, G3T, 1, 5, 8, 16, 16, 0, 8, 1)   \
+    X(28, G2S1, 1, 5, 8, 16, 8, 0, 8, 1)   \
+    X(29, G2S1, 1, 5, 8, 16, 16, 0, 8, 1)  \
+    X(30, G2S1, 2, 5, 8, 16, 16, 0, 8, 1)  \
+    X(31, G2D, 1, 1, 32, 32, 8, 0, 8, 1)   \
+    X(33, G2P, 1, 1, 32, 32, 8, 0, 8, 1)
 
 // "team" configurations (KT teams of NW waves per workgroup, see the kernel header): what a few-tile layer runs on INSTEAD of a split-K launch + splitk_finish.
 // Same (geo, NT, TY, TX, CG) as a split-K configuration -- the packs and tap tables do not depend on TZ.  Small blocks (64 grid points, two waves per team):
 // a team launch has 1 / KT of the split-K launch's workgroups, and these layers are latency chains on a mostly idle chip -- first measured with the split-K
 // blocks (320 points, four waves per team): the teams of a workgroup share their SIMDs' matrix pipes, 14.1 us against 11.5 + the finish launch.
-//        id  geo   NT  TZ TY  TX  CG  PIPE NW KT
 #define DFFW_TILE_CONFIGS_TEAM(X)           \
     X(50, G3S1, 1, 1, 4, 16, 16, 1, 2, 2)   \
     X(51, G3S1, 1, 1, 4, 16, 16, 1, 2, 4)   \
@@ -970,32 +958,117 @@ __global__ __launch_bounds__(NWAVES * KT * 64) void conv_tile(const ConvArgs a, 
     X(61, G3T, 2, 1, 4, 16, 32, 1, 2, 4)
 // (built and dropped, batch 1 / 2 layer tables in profiles/r06_batch1_teams.txt: the 2 x 4 x 8 blocks of the 8 x 8-grid layers with 128-192 input channels, 4 and 8
 // teams of two or three stages each -- 40-96 workgroups walk what split-K spreads over 192: combine2 27.9 against 24.1 us, conv4 21-41 against 19-22)
+#define DFFW_TILE_CONFIGS_ALL(X) DFFW_TILE_CONFIGS(X) DFFW_TILE_CONFIGS_W8(X) DFFW_TILE_CONFIGS_TEAM(X)   // (this order is tile_cfg_find's preference)
+constexpr int TILE_IDS = 64;   // ids are below this
 
-#if DFFW_TILE_PREC == 0 && !defined(DFFW_TILE_LEAN)   // configuration table and look-ups live in one of the per-precision objects
-bool tile_cfg_has_sums(const TileCfg *c) { return c && c->geo == G2S1 && c->nw == 4 && (c->id == 34 || c->id == 19); }
-bool tile_cfg_has_splitk(const TileCfg *c) {
-    switch (c->id) {
-#define X_HAS(ID, GEO, NT, TZ, TY, TX, CG, PIPE) case ID:
-        DFFW_TILE_CONFIGS_SPLITK(X_HAS)
-#undef X_HAS
-        return c->nw == 4;
-        default: return false;
-    }
+// ---- variants: the further instantiations of a configuration, as lists of ids ----
+// PLAIN exists for every configuration in every arithmetic, LEAN for every configuration in split-bf16 (dffw_conv_tile_p0l.o).  The other three are the
+// kernel's SPLITK = true instantiations (see its header for what that flag means per geometry), in every arithmetic:
+// SPLITK: the 4-wave configurations few-tile layers end up on after the channel split (3x3x3 at stride 1 and 2, <= 32 output channels per workgroup)
+#define DFFW_TILE_IDS_SPLITK 0, 1, 2, 16, 5, 6, 17, 38, 39
+// SUMS: the row-sums variant of the per-slice 1x3x3 configurations the alignment heads' third conv runs on
+#define DFFW_TILE_IDS_SUMS 34, 19
+// RAW: the stem reading a raw (uint8 / 0..255) stack
+#define DFFW_TILE_IDS_RAW 15, 31, 32, 33
+// configurations whose LEAN instantiation select_tile() never takes (these two transposed-conv configurations need 7 / 10 registers more with it: a
+// wave per SIMD lost); it is built like the others
+#define DFFW_TILE_IDS_NO_LEAN 23, 27
+
+template <int ID>
+struct TileTuple;   // the line of configuration ID
+#define X_TUPLE(ID, GEO, NT, TZ, TY, TX, CG, PIPE, NW, KT) \
+    template <>                                            \
+    struct TileTuple<ID> { static constexpr int geo = GEO, nt = NT, tz = TZ, ty = TY, tx = TX, cg = CG, pipe = PIPE, nw = NW, kt = KT; };
+DFFW_TILE_CONFIGS_ALL(X_TUPLE)
+#undef X_TUPLE
+
+// One instantiation: what a launch of it reports, the kernel and its block size (KernelRow of dffw_persist.h, with the name held in the row: it is
+// printed once, from the same TileTuple the kernel is instantiated from, exactly as rocprofv3 --kernel-trace prints the instantiation -- all twelve
+// template arguments, which bench.py, the dispatch pins and the tests match on)
+struct TileRow {
+    char name[80];
+    void (*fn)(ConvArgs, TileArgs);
+    int block;
+    TileVariant variant;
+};
+// rows by [arithmetic][variant][configuration id], null where no such instantiation exists
+struct TileIndex {
+    const TileRow *at[3][TILE_VARIANTS][TILE_IDS];
+};
+
+template <int PREC, int ID, TileVariant V>
+static const TileRow *tile_row() {
+    using C = TileTuple<ID>;
+    constexpr bool STEM = C::geo == G2D || C::geo == G2P;
+    constexpr bool SPLITK = V == TileVariant::SPLITK || V == TileVariant::RAW || V == TileVariant::SUMS, LEAN = V == TileVariant::LEAN;
+    static_assert(ID < TILE_IDS, "raise TILE_IDS");
+    static_assert(V != TileVariant::LEAN || PREC == P_BF16X3, "LEAN exists in split-bf16 only");
+    static_assert((V == TileVariant::SUMS) == (SPLITK && C::geo == G2S1) && (V == TileVariant::RAW) == (SPLITK && STEM), "what SPLITK = true means is the geometry's");
+    static const TileRow row = [] {
+        TileRow r;
+        snprintf(r.name, sizeof r.name, "dffw::conv_tile<%d, %d, %d, %d, %d, %d, %d, %d, %d, %s, %s, %d>", PREC, C::geo, C::nt, C::tz, C::ty, C::tx, C::cg, C::pipe,
+                 C::nw, SPLITK ? "true" : "false", LEAN ? "true" : "false", C::kt);
+        r.fn = conv_tile<PREC, C::geo, C::nt, C::tz, C::ty, C::tx, C::cg, C::pipe, C::nw, SPLITK, LEAN, C::kt>;
+        r.block = 64 * C::nw * C::kt;
+        r.variant = V;
+        return r;
+    }();
+    return &row;
+}
+template <int PREC, TileVariant V, int... IDS>
+static void tile_rows(TileIndex &ix) {
+    ((ix.at[PREC][(int)V][IDS] = tile_row<PREC, IDS, V>()), ...);
 }
 
-#define X_CFG(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                             \
+// This source is compiled four times (see the Makefile): one object per arithmetic (-DDFFW_TILE_PREC=0/1/2) and the LEAN instantiations of split-bf16 as a
+// fourth (-DDFFW_TILE_LEAN), so the ~40 kernel instantiations of each build in parallel.  Each object enters the rows of its own instantiations.
+#define X_ID(ID, ...) , ID
+#ifdef DFFW_TILE_LEAN
+void tile_rows_lean0(TileIndex &ix) { tile_rows<P_BF16X3, TileVariant::LEAN DFFW_TILE_CONFIGS_ALL(X_ID)>(ix); }
+#else
+#define DFFW_CAT2(a, b) a##b
+#define DFFW_CAT(a, b) DFFW_CAT2(a, b)
+void DFFW_CAT(tile_rows_prec, DFFW_TILE_PREC)(TileIndex &ix) {
+    tile_rows<DFFW_TILE_PREC, TileVariant::PLAIN DFFW_TILE_CONFIGS_ALL(X_ID)>(ix);
+    tile_rows<DFFW_TILE_PREC, TileVariant::SPLITK, DFFW_TILE_IDS_SPLITK>(ix);
+    tile_rows<DFFW_TILE_PREC, TileVariant::SUMS, DFFW_TILE_IDS_SUMS>(ix);
+    tile_rows<DFFW_TILE_PREC, TileVariant::RAW, DFFW_TILE_IDS_RAW>(ix);
+}
+#endif
+#undef X_ID
+
+#if DFFW_TILE_PREC == 0 && !defined(DFFW_TILE_LEAN)   // the configuration table, the look-ups and the launch live in one of the objects
+void tile_rows_prec1(TileIndex &ix);
+void tile_rows_prec2(TileIndex &ix);
+void tile_rows_lean0(TileIndex &ix);
+static const TileIndex &tile_index() {
+    static const TileIndex ix = [] {
+        TileIndex ix = {};
+        tile_rows_prec0(ix);
+        tile_rows_prec1(ix);
+        tile_rows_prec2(ix);
+        tile_rows_lean0(ix);
+        return ix;
+    }();
+    return ix;
+}
+static const TileRow *tile_row_of(int prec, TileVariant v, const TileCfg *c) {
+    return c && (prec == P_BF16X3 || prec == P_FP16 || prec == P_BF16) ? tile_index().at[prec][(int)v][c->id] : nullptr;
+}
+// (every arithmetic has the same SPLITK and SUMS rows)
+bool tile_cfg_has_splitk(const TileCfg *c) { return tile_row_of(P_BF16X3, TileVariant::SPLITK, c) != nullptr; }
+bool tile_cfg_has_sums(const TileCfg *c) { return tile_row_of(P_BF16X3, TileVariant::SUMS, c) != nullptr; }
+
+constexpr bool tile_id_in(int id, std::initializer_list<int> ids) {
+    for (int i : ids)
+        if (i == id) return true;
+    return false;
+}
+#define X_CFG(ID, GEO, NT, TZ, TY, TX, CG, PIPE, NW, KT)                                                     \
     TileCfg{ID, GEO, NT, CG, TZ, TY, TX, TileT<GEO, TZ, TY, TX, CG>::FZ, TileT<GEO, TZ, TY, TX, CG>::FY, \
-            TileT<GEO, TZ, TY, TX, CG>::FX, TileT<GEO, TZ, TY, TX, CG>::FXL, PIPE, 4},
-#define X_CFG8(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                            \
-    TileCfg{ID, GEO, NT, CG, TZ, TY, TX, TileT<GEO, TZ, TY, TX, CG>::FZ, TileT<GEO, TZ, TY, TX, CG>::FY, \
-            TileT<GEO, TZ, TY, TX, CG>::FX, TileT<GEO, TZ, TY, TX, CG>::FXL, PIPE, 8},
-#define X_CFGT(ID, GEO, NT, TZ, TY, TX, CG, PIPE, NW, KT)                                                    \
-    TileCfg{ID, GEO, NT, CG, TZ, TY, TX, TileT<GEO, TZ, TY, TX, CG>::FZ, TileT<GEO, TZ, TY, TX, CG>::FY, \
-            TileT<GEO, TZ, TY, TX, CG>::FX, TileT<GEO, TZ, TY, TX, CG>::FXL, PIPE, NW, KT},
-static const TileCfg g_cfgs[] = {DFFW_TILE_CONFIGS(X_CFG) DFFW_TILE_CONFIGS_W8(X_CFG8) DFFW_TILE_CONFIGS_TEAM(X_CFGT)};
+            TileT<GEO, TZ, TY, TX, CG>::FX, TileT<GEO, TZ, TY, TX, CG>::FXL, PIPE, NW, KT, !tile_id_in(ID, {DFFW_TILE_IDS_NO_LEAN})},
+static const TileCfg g_cfgs[] = {DFFW_TILE_CONFIGS_ALL(X_CFG)};
 #undef X_CFG
-#undef X_CFG8
-#undef X_CFGT
 
 int tile_cfg_count() { return (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0])); }
 const TileCfg *tile_cfg_at(int i) { return (i >= 0 && i < tile_cfg_count()) ? &g_cfgs[i] : nullptr; }
@@ -1029,125 +1102,45 @@ const TileCfg *tile_cfg_find_team(const TileCfg *base, int nstage, int nt) {
     return nullptr;
 }
 
-// the launch takes the LEAN instantiation (straight-line epilogue): split-bf16 storage, no split-K / raw-stack / row-sums variant,
+// The instantiation a launch runs.  LEAN (straight-line epilogue) where it covers the launch: split-bf16 storage, no split-K / raw-stack / row-sums variant,
 // something to write, ReLU (if any) after the residual, at most one residual in the output's own geometry, and EVERY 16-channel
 // result tile of the layer a real one (the straight-line epilogue has no per-tile channel guard: Cout = 48 / 80 / 96 / 112 are packed as 4 / 8
 // tiles whose padding tiles must not store; a channel-split launch, c->nt < nt_total, walks real tiles only) or the packed 8-channel form
-bool tile_lean(int prec, const TileCfg *c, const ConvArgs &a, const TileArgs &t) {
-    return prec == P_BF16X3 && t.ksplit <= 1 && !(a.dbg & (DFFW_ARGS_RAW | DFFW_ARGS_SUMS)) && (a.out || a.out_pre || a.cls_w) && !a.outf && !a.res1 &&
-           !a.res_bcast && a.relu != 2 && (a.Cout == t.nt_total * 16 || (a.Cout == 8 && c->nt == 1)) && !(a.dbg & DFFW_ARGS_NO_LEAN_TILE) &&
-           c->id != 23 && c->id != 27;   // (these two transposed-conv configurations need 7 / 10 registers more with it: a wave per SIMD lost)
+static const TileRow *select_tile(int prec, const TileCfg *c, const ConvArgs &a, const TileArgs &t) {
+    if (!c) return nullptr;
+    const bool lean = prec == P_BF16X3 && t.ksplit <= 1 && !(a.dbg & (DFFW_ARGS_RAW | DFFW_ARGS_SUMS)) && (a.out || a.out_pre || a.cls_w) && !a.outf && !a.res1 &&
+                      !a.res_bcast && a.relu != 2 && (a.Cout == t.nt_total * 16 || (a.Cout == 8 && c->nt == 1)) && !(a.dbg & DFFW_ARGS_NO_LEAN_TILE) && c->lean;
+    const TileVariant v = lean                        ? TileVariant::LEAN
+                          : t.ksplit > 1              ? TileVariant::SPLITK
+                          : (a.dbg & DFFW_ARGS_SUMS) ? TileVariant::SUMS
+                          : (a.dbg & DFFW_ARGS_RAW)  ? TileVariant::RAW
+                                                      : TileVariant::PLAIN;
+    return tile_row_of(prec, v, c);
 }
 
-void conv_tile_kernel_name(int prec, const TileCfg *c, bool splitk, bool lean, char *buf, int n) {
-    // exactly as rocprofv3 --kernel-trace prints the instantiation (all twelve template arguments)
-    snprintf(buf, n, "dffw::conv_tile<%d, %d, %d, %d, %d, %d, %d, %d, %d, %s, %s, %d>", prec, c->geo, c->nt, c->tz, c->ty, c->tx, c->cg, c->pipe, c->nw,
-             splitk ? "true" : "false", lean ? "true" : "false", c->kt > 1 ? c->kt : 1);
-}
-
-#endif
-
-#ifdef DFFW_TILE_LEAN
-// ---- the LEAN instantiations of the split-bf16 arithmetic: their own object (dffw_conv_tile_p0l.o), built beside the others ----
-hipError_t launch_conv_tile_lean0(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s) {
-    switch (cfg->id) {
-#define X_LAUNCH(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                                       \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<P_BF16X3, GEO, NT, TZ, TY, TX, CG, PIPE, 4, false, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.pass_split ? 4 : 1)), dim3(256), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS(X_LAUNCH)
-#undef X_LAUNCH
-#define X_LAUNCH8(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                                      \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<P_BF16X3, GEO, NT, TZ, TY, TX, CG, PIPE, 8, false, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.pass_split ? 4 : 1)), dim3(512), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS_W8(X_LAUNCH8)
-#undef X_LAUNCH8
-#define X_LAUNCHT(ID, GEO, NT, TZ, TY, TX, CG, PIPE, NW, KT)                                                              \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<P_BF16X3, GEO, NT, TZ, TY, TX, CG, PIPE, NW, false, true, KT>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.pass_split ? 4 : 1)), dim3(64 * NW * KT), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS_TEAM(X_LAUNCHT)
-#undef X_LAUNCHT
-        default: return hipErrorInvalidValue;
+static dim3 tile_grid(TileVariant v, const TileArgs &t) {
+    switch (v) {
+        case TileVariant::SPLITK: return dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)t.ksplit);
+        case TileVariant::SUMS: return dim3((unsigned)t.grid, 1, 1);
+        case TileVariant::RAW: return dim3((unsigned)t.grid, (unsigned)t.nsplit, 1);
+        default: return dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.pass_split ? 4 : 1));
     }
-    return hipGetLastError();
-}
-#else
-template <int PREC>
-static hipError_t launch_conv_tile_p(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s) {
-    switch (t.ksplit > 1 ? 1000 + cfg->id : ((a.dbg & DFFW_ARGS_SUMS) ? 3000 + cfg->id : ((a.dbg & DFFW_ARGS_RAW) ? 2000 + cfg->id : cfg->id))) {
-#define X_LAUNCH(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                                       \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<PREC, GEO, NT, TZ, TY, TX, CG, PIPE>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.ksplit > 1 ? t.ksplit : (t.pass_split ? 4 : 1))), dim3(256), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS(X_LAUNCH)
-#undef X_LAUNCH
-#define X_LAUNCH8(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                                      \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<PREC, GEO, NT, TZ, TY, TX, CG, PIPE, 8>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.ksplit > 1 ? t.ksplit : (t.pass_split ? 4 : 1))), dim3(512), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS_W8(X_LAUNCH8)
-#undef X_LAUNCH8
-#define X_LAUNCHK(ID, GEO, NT, TZ, TY, TX, CG, PIPE)                                                                      \
-    case 1000 + ID:                                                                                                 \
-        hipLaunchKernelGGL((conv_tile<PREC, GEO, NT, TZ, TY, TX, CG, PIPE, 4, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)t.ksplit), dim3(256), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS_SPLITK(X_LAUNCHK)
-#undef X_LAUNCHK
-#define X_LAUNCHT(ID, GEO, NT, TZ, TY, TX, CG, PIPE, NW, KT)                                                              \
-    case ID:                                                                                                        \
-        hipLaunchKernelGGL((conv_tile<PREC, GEO, NT, TZ, TY, TX, CG, PIPE, NW, false, false, KT>), dim3((unsigned)t.grid, (unsigned)t.nsplit, (unsigned)(t.pass_split ? 4 : 1)), dim3(64 * NW * KT), 0, s, a, t); \
-        break;
-        DFFW_TILE_CONFIGS_TEAM(X_LAUNCHT)
-#undef X_LAUNCHT
-        // the row-sums variant of the per-slice 1x3x3 configurations the alignment heads' third conv runs on
-        case 3000 + 34:
-            hipLaunchKernelGGL((conv_tile<PREC, G2S1, 2, 5, 4, 16, 32, 1, 4, true>), dim3((unsigned)t.grid, 1, 1), dim3(256), 0, s, a, t);
-            break;
-        case 3000 + 19:
-            hipLaunchKernelGGL((conv_tile<PREC, G2S1, 4, 5, 4, 16, 16, 1, 4, true>), dim3((unsigned)t.grid, 1, 1), dim3(256), 0, s, a, t);
-            break;
-        // the stem reading a raw (uint8 / 0..255) stack: its "SPLITK" instantiations
-        case 2000 + 15:
-            hipLaunchKernelGGL((conv_tile<PREC, G2D, 1, 1, 16, 32, 8, 0, 4, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, 1), dim3(256), 0, s, a, t);
-            break;
-        case 2000 + 31:
-            hipLaunchKernelGGL((conv_tile<PREC, G2D, 1, 1, 32, 32, 8, 0, 8, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, 1), dim3(512), 0, s, a, t);
-            break;
-        case 2000 + 32:
-            hipLaunchKernelGGL((conv_tile<PREC, G2P, 1, 1, 16, 32, 8, 0, 4, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, 1), dim3(256), 0, s, a, t);
-            break;
-        case 2000 + 33:
-            hipLaunchKernelGGL((conv_tile<PREC, G2P, 1, 1, 32, 32, 8, 0, 8, true>), dim3((unsigned)t.grid, (unsigned)t.nsplit, 1), dim3(512), 0, s, a, t);
-            break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
 }
 
-// This source is compiled three times (-DDFFW_TILE_PREC=0/1/2, see the Makefile): one object per arithmetic, so the
-// ~40 kernel instantiations of each build in parallel.
-#define DFFW_CAT2(a, b) a##b
-#define DFFW_CAT(a, b) DFFW_CAT2(a, b)
-hipError_t DFFW_CAT(launch_conv_tile_prec, DFFW_TILE_PREC)(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s) {
-    return launch_conv_tile_p<DFFW_TILE_PREC>(cfg, a, t, s);
-}
-
-#if DFFW_TILE_PREC == 0
-hipError_t launch_conv_tile_prec1(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s);
-hipError_t launch_conv_tile_prec2(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s);
-hipError_t launch_conv_tile_lean0(const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s);
 hipError_t launch_conv_tile(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, hipStream_t s) {
-    if (tile_lean(prec, cfg, a, t)) return launch_conv_tile_lean0(cfg, a, t, s);
-    switch (prec) {
-        case P_BF16X3: return launch_conv_tile_prec0(cfg, a, t, s);
-        case P_FP16: return launch_conv_tile_prec1(cfg, a, t, s);
-        case P_BF16: return launch_conv_tile_prec2(cfg, a, t, s);
-    }
-    return hipErrorInvalidValue;
+    const TileRow *row = select_tile(prec, cfg, a, t);
+    if (!row) return hipErrorInvalidValue;
+    // what the team form takes for granted (see the kernel header): one stage per team, the contraction not split over workgroups as well, and ONE pass per
+    // workgroup -- a team other than team 0 leaves the pass loop after its first pass, so a transposed conv must have its passes split over grid.z
+    if (cfg->kt > 1 && (t.nstage != cfg->kt || t.ksplit > 1 || (cfg->geo == G3T && !t.pass_split))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(row->fn, tile_grid(row->variant, t), dim3(row->block), 0, s, a, t);
+    return hipGetLastError();
+}
+
+void conv_tile_kernel_name(int prec, const TileCfg *cfg, const ConvArgs &a, const TileArgs &t, char *buf, int n) {
+    const TileRow *row = select_tile(prec, cfg, a, t);
+    if (n > 0) snprintf(buf, n, "%s", row ? row->name : "");
 }
 #endif
-#endif   // DFFW_TILE_LEAN
 
 }  // namespace dffw

@@ -321,12 +321,23 @@ void Planner::tile(ConvPlan &p, const TilePack &tp, bool stem_pair, int gH, int 
         t.oox[ps] = tp.oox[ps];
         flops += 2.0 * (double)a.M * (L.transposed ? tp.ntaps[ps] : L.kd * L.kh * L.kw) * L.cin * L.cout;
     }
-    t.tiles_z = (a.Ng + cfg->tz - 1) / cfg->tz;
-    t.tiles_y = (a.Hg + cfg->ty - 1) / cfg->ty;
-    t.tiles_x = (a.Wg + cfg->tx - 1) / cfg->tx;
-    t.total_tiles = a.B * t.tiles_z * t.tiles_y * t.tiles_x;
     t.nt_total = pc.nt;
     t.nsplit = pc.nt / cfg->nt;   // (1, except the narrow packs of layers with more than 4 output tiles)
+    // the tiles of configuration `c` on this grid, one per workgroup with the launch a multiple of the 8 XCDs, and whether the t.nsplit workgroups of each are
+    // few enough to warm their weights (so: called again when t.nsplit has changed)
+    auto set_tiles = [&](const TileCfg *c) {
+        t.tiles_z = (a.Ng + c->tz - 1) / c->tz;
+        t.tiles_y = (a.Hg + c->ty - 1) / c->ty;
+        t.tiles_x = (a.Wg + c->tx - 1) / c->tx;
+        t.total_tiles = a.B * t.tiles_z * t.tiles_y * t.tiles_x;
+        t.grid = 8 * ((t.total_tiles + 7) / 8);
+        t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
+    };
+    // workgroups of a launch on the team configuration `c` with `nsplit` output-channel workgroups per tile and `npass` passes over grid.z
+    auto team_wgs = [&](const TileCfg *c, int nsplit, int npass) {
+        return (int64_t)a.B * ((a.Ng + c->tz - 1) / c->tz) * ((a.Hg + c->ty - 1) / c->ty) * ((a.Wg + c->tx - 1) / c->tx) * nsplit * npass;
+    };
+    set_tiles(cfg);
     // few-tile layers (the 1/16..1/32-resolution pyramid, or batch 1): split the output channels over
     // grid.y so that at least ~one workgroup per CU exists
     // (3x3x3 stride-1 and transposed layers also at exactly one tile per CU -- the 16x16-grid layers at batch 32: two 32-channel
@@ -337,19 +348,18 @@ void Planner::tile(ConvPlan &p, const TilePack &tp, bool stem_pair, int gH, int 
     if (t.total_tiles < split_below && pc.nt > 1 && !o.cls && !sw.on(SW_NO_SPLIT)) {
         const int want = (256 + t.total_tiles - 1) / t.total_tiles;   // split factor that would fill the chip (narrow blocks: 512 measured level)
         for (int nts = pc.nt / 2; nts >= 1; nts /= 2) {               // coarsest split first
-            const TileCfg *c2 = tile_cfg_find_like(tp.cfg, nts);
+            const TileCfg *c2 = pc.nt % nts == 0 ? tile_cfg_find_like(tp.cfg, nts) : nullptr;   // (whole splits only)
             if (!c2) continue;
             cfg = c2;
             t.nsplit = pc.nt / nts;
             if (t.nsplit >= want) break;
         }
+        set_tiles(cfg);   // (the same tiles: find_like keeps the block shape)
     }
-    t.grid = 8 * ((t.total_tiles + 7) / 8);   // one tile per workgroup, grid a multiple of the 8 XCDs
     // split-K: when even the channel split leaves most CUs idle and the contraction is several channel-group
     // stages deep, the stages are dealt to grid.z workgroups (fp32 partials, summed in fixed order by
     // splitk_finish) so that one workgroup no longer walks all of them in sequence
     t.ksplit = 1;
-    t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
     p.M_out = (int64_t)out.B * No * Ho * Wo;
     // transposed conv on few tiles: its 4 sub-pixel passes as 4 workgroups (no reduction, any epilogue)
     const int thr = sw.split_wg;
@@ -358,17 +368,11 @@ void Planner::tile(ConvPlan &p, const TilePack &tp, bool stem_pair, int gH, int 
         // a transposed layer whose passes are workgroups of their own walks its 2-4 channel-group stages one after the other (SPP conv8 at batch 1:
         // 30 us): one stage per team instead, with as few output-channel workgroups per tile as keep the launch to one round of workgroups
         for (int nts = cfg->nt; nts <= pc.nt && nts <= 2; nts *= 2) {
-            const TileCfg *team = tile_cfg_find_team(cfg, tp.nstage, nts);
-            if (!team) continue;
-            const int tz_t = (a.Ng + team->tz - 1) / team->tz, ty_t = (a.Hg + team->ty - 1) / team->ty, tx_t = (a.Wg + team->tx - 1) / team->tx;
-            const int64_t wgs = (int64_t)a.B * tz_t * ty_t * tx_t * (pc.nt / nts) * 4;
-            if (wgs > sw.team_max_wgs) continue;
+            const TileCfg *team = pc.nt % nts == 0 ? tile_cfg_find_team(cfg, tp.nstage, nts) : nullptr;   // (whole splits only)
+            if (!team || team_wgs(team, pc.nt / nts, 4) > sw.team_max_wgs) continue;
             cfg = team;
             t.nsplit = pc.nt / nts;
-            t.tiles_z = tz_t; t.tiles_y = ty_t; t.tiles_x = tx_t;
-            t.total_tiles = a.B * tz_t * ty_t * tx_t;
-            t.grid = 8 * ((t.total_tiles + 7) / 8);
-            t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
+            set_tiles(cfg);
             break;
         }
     }
@@ -384,19 +388,13 @@ void Planner::tile(ConvPlan &p, const TilePack &tp, bool stem_pair, int gH, int 
         if (team) {
             // ... unless the team launch needs several rounds of workgroups (their LDS images allow one or two per CU, and next to the other streams'
             // kernels they take whole CUs): measured per layer at batch 1 / 2 / 4, profiles/r06_batch1_teams.txt
-            const int tz_t = (a.Ng + team->tz - 1) / team->tz;
-            const int64_t wgs = (int64_t)a.B * tz_t * ((a.Hg + team->ty - 1) / team->ty) * ((a.Wg + team->tx - 1) / team->tx) * t.nsplit;
+            const int64_t wgs = team_wgs(team, t.nsplit, 1);
             if (wgs < sw.team_min_wgs || wgs > sw.team_max_wgs) team = nullptr;
         }
         if (team) {
             cfg = team;
             t.ksplit = 1;
-            t.tiles_z = (a.Ng + cfg->tz - 1) / cfg->tz;
-            t.tiles_y = (a.Hg + cfg->ty - 1) / cfg->ty;
-            t.tiles_x = (a.Wg + cfg->tx - 1) / cfg->tx;
-            t.total_tiles = a.B * t.tiles_z * t.tiles_y * t.tiles_x;
-            t.grid = 8 * ((t.total_tiles + 7) / 8);
-            t.warm = (t.total_tiles * t.nsplit <= sw.warm_max_wgs) ? 1 : 0;
+            set_tiles(cfg);
         }
         if (t.ksplit > 1) {
             t.partial_stride = p.M_out * (int64_t)pc.nt * 16;
@@ -416,7 +414,7 @@ void Planner::tile(ConvPlan &p, const TilePack &tp, bool stem_pair, int gH, int 
     l.flops = flops;
     l.bytes = in_b + (o.outf ? opx * L.cout * 4.0 : out_b(o.out_pre ? 2 : 1)) + out_b(res(o.res0) + res(o.res1)) + w_b((double)L.kd * L.kh * L.kw);
     if (p.stem_pipe) stem_pipe_kernel_name(a, l.kernel, sizeof l.kernel);
-    else conv_tile_kernel_name(prec, cfg, t.ksplit > 1 || (a.dbg & (DFFW_ARGS_RAW | DFFW_ARGS_SUMS)), tile_lean(prec, cfg, a, t), l.kernel, sizeof l.kernel);
+    else conv_tile_kernel_name(prec, cfg, a, t, l.kernel, sizeof l.kernel);
 }
 
 // the gather kernels (conv_igemm / conv_small): one launch per variant (a regular conv, or one sub-pixel phase of a transposed one)
@@ -438,7 +436,7 @@ void Planner::gather(ConvPlan &p) {
             a.ooy = a.oox = 0;
         }
         a.M = (int64_t)a.B * a.Ng * a.Hg * a.Wg;
-        if (sw.on(SW_NO_SMALL)) a.dbg |= 32;   // (bit 5 of dbg: conv_igemm also for small grids)
+        if (sw.on(SW_NO_SMALL)) a.dbg |= DFFW_ARGS_NO_SMALL;
         ConvLaunch &l = p.l[p.n++];
         l.a = a;
         l.suffix = "";

@@ -47,6 +47,7 @@ struct RawStack {
 #define DFFW_ARGS_SUMS 128
 // kernel-path switches of the forward's snapshot (Switches, dffw_engine.cpp) that the launchers consult: carried in ConvArgs::dbg so that the
 // kernel name reported and the instantiation launched cannot disagree (no getenv at launch time)
+#define DFFW_ARGS_NO_SMALL 32       // DFFW_NO_SMALL: conv_igemm also for the small grids that conv_small serves
 #define DFFW_ARGS_NO_LEAN_TILE 16   // DFFW_NO_LEAN_TILE: conv_tile's generic epilogue instead of its LEAN instantiations
 #define DFFW_ARGS_NO_LEAN_ROLL 64   // DFFW_NO_LEAN_ROLL: the same for the rolling-window kernels
 #define DFFW_ARGS_NO_ROLLX 256   // DFFW_NO_ROLLX: conv_roll's serial step instead of conv_rollx's pipelined one
@@ -89,7 +90,6 @@ struct ConvArgs {
 // launchers (dffw_kernels.hip)
 int conv_nt_for(int cout);  // 16-channel output tiles the conv kernel picked for `cout` iterates over
 hipError_t launch_conv(int prec, const ConvArgs &a, hipStream_t s);
-void conv_kernel_name(int prec, int cout, char *buf, int n);  // name of the instantiation launch_conv picks
 void conv_kernel_name_for(int prec, const ConvArgs &a, char *buf, int n);   // name of the kernel launch_conv picks for `a` (conv_small for small grids)
 hipError_t launch_set_raw(const RawStack &rs, RawStack *dst, hipStream_t s);   // writes the descriptor into device memory (enqueue-only)
 hipError_t launch_stack_in(int prec, const float *FS, uint16_t *out, int B, int N, int H, int W, hipStream_t s);

@@ -13,6 +13,7 @@
 
 #include "dffw_device.h"
 #include "dffw_internal.h"
+#include "dffw_persist.h"
 
 namespace dffw {
 
@@ -218,63 +219,52 @@ static bool conv_small_wanted(const ConvArgs &a) {
     return !a.cls_w && tiles <= 4096 && a.KC >= 1;
 }
 
-template <int PREC>
-static hipError_t launch_conv_small(const ConvArgs &a, hipStream_t s) {
-    const int nt = conv_nt_for(a.Cout);           // weights are packed for this many 16-channel output tiles
-    const int nt_live = (a.Cout + 15) / 16;       // ... of which these carry channels
-    const dim3 grid((unsigned)((a.M + 15) / 16), (unsigned)nt);
-    (void)nt_live;
-    if (a.KC >= 8) hipLaunchKernelGGL((conv_small<PREC, 8>), grid, dim3(512), 0, s, a);
-    else if (a.KC >= 4) hipLaunchKernelGGL((conv_small<PREC, 4>), grid, dim3(256), 0, s, a);
-    else if (a.KC >= 2) hipLaunchKernelGGL((conv_small<PREC, 2>), grid, dim3(128), 0, s, a);
-    else hipLaunchKernelGGL((conv_small<PREC, 1>), grid, dim3(64), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int PREC, int NT, int MT>
-static hipError_t launch_conv_t(const ConvArgs &a, hipStream_t s) {
-    const int64_t per_wg = 4 * MT * 16;
-    const int64_t grid = (a.M + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL((conv_igemm<PREC, NT, MT>), dim3((unsigned)grid), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int PREC>
-static hipError_t launch_conv_p(const ConvArgs &a, hipStream_t s) {
-    if (conv_small_wanted(a) && !(a.dbg & 32)) return launch_conv_small<PREC>(a, s);
-    const int nt = (a.Cout + 15) / 16;
-    if (nt <= 1) return launch_conv_t<PREC, 1, 4>(a, s);
-    if (nt <= 2) return launch_conv_t<PREC, 2, 4>(a, s);
-    if (nt <= 4) return launch_conv_t<PREC, 4, 4>(a, s);
-    if (nt <= 8) return launch_conv_t<PREC, 8, 2>(a, s);
-    return hipErrorInvalidValue;
-}
-
 // number of 16-channel output tiles the kernel chosen for `cout` iterates over (weights are packed for it)
 int conv_nt_for(int cout) {
     const int nt = (cout + 15) / 16;
     return nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : 8;
 }
 
-void conv_kernel_name(int prec, int cout, char *buf, int n) {
-    const int nt = conv_nt_for(cout);
-    snprintf(buf, n, "dffw::conv_igemm<%d, %d, %d>", prec, nt, nt == 8 ? 2 : 4);
-}
+// the instantiations, [precision][sub]: conv_small by its KS waves (each a share of the contraction), conv_igemm by its NT output tiles with the MT operand
+// tiles a wave walks (a workgroup: 4 waves x MT tiles x 16 pixels)
+using ConvRow = KernelRow<ConvArgs>;
+#define R(P) DFFW_ROW(64, conv_small, P, 1), DFFW_ROW(128, conv_small, P, 2), DFFW_ROW(256, conv_small, P, 4), DFFW_ROW(512, conv_small, P, 8)
+static const ConvRow kSmall[] = {R(0), R(1), R(2)};
+#undef R
+struct IgemmRow {
+    ConvRow row;
+    int mt;
+};
+#define R_(P, NT, MT) {DFFW_ROW(256, conv_igemm, P, NT, MT), MT}
+#define R(P) R_(P, 1, 4), R_(P, 2, 4), R_(P, 4, 4), R_(P, 8, 2)
+static const IgemmRow kIgemm[] = {R(0), R(1), R(2)};
+#undef R
+#undef R_
 
-// name of the kernel launch_conv picks for these arguments (conv_small for small grids, else conv_igemm)
-void conv_kernel_name_for(int prec, const ConvArgs &a, char *buf, int n) {
-    if (conv_small_wanted(a) && !(a.dbg & 32)) snprintf(buf, n, "dffw::conv_small<%d, %d>", prec, a.KC >= 8 ? 8 : a.KC >= 4 ? 4 : a.KC >= 2 ? 2 : 1);
-    else conv_kernel_name(prec, a.Cout, buf, n);
+// the row a launch runs and its grid; a null row: nothing is instantiated for these arguments
+struct ConvChoice {
+    const ConvRow *row;
+    dim3 grid;
+};
+static ConvChoice select_conv(int prec, const ConvArgs &a) {
+    const int nt = conv_nt_for(a.Cout);           // weights are packed for this many 16-channel output tiles
+    if (conv_small_wanted(a) && !(a.dbg & DFFW_ARGS_NO_SMALL))
+        return {prec_row(kSmall, prec, 4, a.KC >= 8 ? 3 : a.KC >= 4 ? 2 : a.KC >= 2 ? 1 : 0), dim3((unsigned)((a.M + 15) / 16), (unsigned)nt)};
+    const IgemmRow *r = a.Cout <= 8 * 16 ? prec_row(kIgemm, prec, 4, nt == 8 ? 3 : nt == 4 ? 2 : nt == 2 ? 1 : 0) : nullptr;
+    if (!r) return {nullptr, dim3()};
+    const int64_t per_wg = 4 * r->mt * 16;
+    return {&r->row, dim3((unsigned)((a.M + per_wg - 1) / per_wg))};
 }
 
 hipError_t launch_conv(int prec, const ConvArgs &a, hipStream_t s) {
-    switch (prec) {
-        case P_BF16X3: return launch_conv_p<P_BF16X3>(a, s);
-        case P_FP16: return launch_conv_p<P_FP16>(a, s);
-        case P_BF16: return launch_conv_p<P_BF16>(a, s);
-    }
-    return hipErrorInvalidValue;
+    const ConvChoice c = select_conv(prec, a);
+    if (!c.row) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(c.row->fn, c.grid, dim3(c.row->block), 0, s, a);
+    return hipGetLastError();
 }
+
+// name of the kernel launch_conv picks for these arguments (conv_small for small grids, else conv_igemm)
+void conv_kernel_name_for(int prec, const ConvArgs &a, char *buf, int n) { copy_row_name(select_conv(prec, a).row, buf, n); }
 
 // ---- layout conversion -------------------------------------------------------------------------
 // focal stack (B,3,N,H,W) fp32 -> paired-pixel volume (B,N,H,W+2) of 8-channel records: record q of a

@@ -367,6 +367,10 @@ def test_hip_e2e_head_tail_as_plane_sums(lib_built, monkeypatch, B, H, W, precis
                 is_sums = got[0].endswith(", true>")          # conv_slice32<RELU, RES, SUMS> / conv_slice64<RELU, SUMS>
             else:
                 is_sums = got[0].rstrip(">").split(", ")[9] == "true"
+                if is_sums:   # the row-sums instantiation of this head's configuration (32 channels: CG 32, 64: CG 16), spelled in full
+                    tile = {"conv2": "2, 5, 4, 16, 32", "conv1": "4, 5, 4, 16, 16"}[lvl]
+                    p = ("bf16x3", "fp16", "bf16").index(precision)
+                    assert got[0] == "dffw::conv_tile<%d, 3, %s, 1, 4, true, false, 1>" % (p, tile), (lvl, got)
             assert is_sums == want, (lvl, got, want)
         monkeypatch.setenv("DFFW_NO_HEAD_SUMS_FUSED", "1")
         with torch.no_grad():

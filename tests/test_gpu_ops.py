@@ -880,6 +880,9 @@ def test_conv_kernels_wide_regimes(eng, row, regime, prec, monkeypatch):
     got = eng.op_conv3d(x.cuda(), w, **geo, bn=bn, residual=res.cuda() if res is not None else None, relu=relu, precision=prec)
     kn = eng.last_conv_kernel()
     assert kn.startswith(prefixes), kn
+    if name in ("tile_generic", "tile_lean"):   # the variant, not only the family (..., SPLITK, LEAN, KT>): LEAN exists in split-bf16 alone
+        lean = name == "tile_lean" and prec == "bf16x3"
+        assert kn.endswith(", false, %s, 1>" % ("true" if lean else "false")), kn
     bounded(got, r, prec, kn, "%s %s" % (name, regime))
     if regime == "impulse":
         zero = r.D == 0

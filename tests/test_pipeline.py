@@ -385,3 +385,37 @@ def test_forward_raw_is_bit_identical_to_pack_then_forward(pl, layout, shape, cr
     for x, y in zip(a64, b64):
         assert torch.equal(x, y)
     assert not torch.equal(a64[3], a[3])
+
+
+@pytest.mark.gpu
+def test_forward_raw_stem_runs_conv_tile_raw_variant(pl, monkeypatch):
+    """The smallest stack the tiled stem serves (B=1, N=2, 32 x 64, uint8) with the persistent stem off (DFFW_NO_STEM_PIPE): forward_raw's stem launch
+    is conv_tile's RAW instantiation -- its tenth template argument, SPLITK, is what the stem geometries build their raw-stack loader from -- while
+    pack_stack + forward runs the same configuration without it; the four outputs are equal bit for bit."""
+    from dffinthewild_amd import graph, synth
+    from dffinthewild_amd.Depth_Estimation_Network import Network
+    entries = list(graph.param_entries(graph.dff_net_convs()))
+    sd = {k: torch.from_numpy(v) for k, v in synth.state_dict_numpy(entries, 0, "smooth").items()}
+    model = Network()
+    model.load_state_dict(sd)
+    model = model.cuda().eval()
+    raw = torch.from_numpy(np.random.RandomState(5).randint(0, 256, size=(1, 2, 32, 64, 3)).astype(np.uint8)).cuda()
+    fd = pl.focus_dists(np.linspace(0.1, 1.5, 2), 1)
+    engine = model._engine_on(raw.device)
+    monkeypatch.setenv("DFFW_NO_STEM_PIPE", "1")
+
+    def stem_args(run):
+        engine.profile(True)
+        out = run()
+        rows = engine.profile_collect()
+        engine.profile(False)
+        ks = [r[0] for r in rows if r[1] == "DFF_net.FM_measure.Focus_extraction.0.0"]
+        assert len(ks) == 1 and ks[0].startswith("dffw::conv_tile<") and ks[0].endswith(">"), rows
+        return out, ks[0][len("dffw::conv_tile<"):-1].split(", ")
+    with torch.no_grad():
+        a, ka = stem_args(lambda: model.forward_raw(raw, fd, "NHWC"))
+        b, kb = stem_args(lambda: model(pl.pack_stack(raw, "NHWC"), fd))
+    assert len(ka) == 12 and ka[9] == "true", ka
+    assert kb[9] == "false" and kb[:9] == ka[:9], (ka, kb)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)

@@ -218,6 +218,15 @@ class Network(nn.Module):
         return self._engine_on(raw.device).forward_raw(ptr, (st[0], st[an], st[ay], st[ax], st[ac]), (0 if raw.dtype == torch.uint8 else 1) | nflag,
                                                        h, w, focus_dists.float(), B, N, H, W)
 
+    _SCORE_TAPS = ("conf", "cost1", "cost2", "cost3")
+
+    def training_loss(self, FS, focus_dists, gt, mask, conf=None, weights=(0.3, 0.5, 0.7, 1.0), depth_range=None, grads=True):
+        """One forward with the four score taps, then pipeline.training_loss on them: (total, per_head, preds, grads), grads being
+        dTotal/d(conf, cost1, cost2, cost3).  Eval mode like forward (BatchNorm runs on its running statistics); forward is unchanged."""
+        from . import pipeline as _pl
+        _, taps = self.forward_with_taps(FS, focus_dists, self._SCORE_TAPS)
+        return _pl.training_loss([taps[k] for k in self._SCORE_TAPS], focus_dists, gt, mask, conf, weights, depth_range, grads)
+
     def forward_with_taps(self, FS, focus_dists, names):
         """Debug variant: also returns {name: tensor} for intermediate volumes (V1, V2, V3,
         FS_volume, conf, cost1, cost2, cost3) in the reference's layout."""

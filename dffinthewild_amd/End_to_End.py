@@ -49,6 +49,12 @@ class Network(_DepthNetwork):
         FS, focus_dists, FOVs = self._check_e2e(FS, focus_dists, FOVs)
         return self._engine_on(FS.device).forward_e2e(FS, focus_dists, FOVs)
 
+    def training_loss(self, FS, focus_dists, FOVs, gt, mask, conf=None, weights=(0.3, 0.5, 0.7, 1.0), depth_range=None, grads=True):
+        """The depth module's training loss on the aligned stack: one forward with the four score taps, then pipeline.training_loss."""
+        from . import pipeline as _pl
+        _, taps = self.forward_with_taps(FS, focus_dists, FOVs, self._SCORE_TAPS)
+        return _pl.training_loss([taps[k] for k in self._SCORE_TAPS], focus_dists, gt, mask, conf, weights, depth_range, grads)
+
     def forward_with_taps(self, FS, focus_dists, FOVs, names):
         """Debug variant: also returns {name: tensor} — head3, head2, head1 (each alpha head before damping) and
         alpha, all (B,3,N), alpha3 / alpha2 (after the level-3 / level-2 heads), fe1 / fe2 / fe3 (the three feature

@@ -436,6 +436,37 @@ __device__ __forceinline__ void epilogue_cls(const ConvArgs &a, float partial, i
     if ((g & (rows - 1)) == 0 && pvalid) a.cls_out[opix] = partial;
 }
 
+// ---- softplus / sigmoid of the regression heads (regress_kernel, regress_fused_kernel, the training loss of dffw_loss.hip) ----
+// softplus (beta 1, threshold 20) = v > 20 ? v : log1p(exp(v)) on the hardware transcendentals instead of libm's
+// expf/log1pf (the regression kernels were bound by those two calls):
+//   e = exp(v) = exp2(v*log2e), the product carried in two floats so that the result keeps ~1 ulp for |v| up to 88;
+//   log1p(e)  = log(w) * e / (w - 1) with w = fl(1 + e) (the classic correction for the rounding of 1 + e: exact-rounded it is within 3.3e-7
+//               of log1p over v in [-30, 20]), e itself where w == 1; v_log_f32 and v_rcp_f32, no branch.  (Rounds 1-3 used a 9-term series below
+//               e = 0.1 and an IEEE division above it: ~55 vector instructions per value with both sides of the divergent branch executed, and
+//               the fused head kernel -- 40 values per pixel -- ran with its vector issue port 1.01 busy, profiles/r04_pmc_conv_kernels.txt.)
+// Measured against torch.nn.functional.softplus in tests/test_gpu_ops.py::test_regression_head (2e-6 rel-L2).
+__device__ __forceinline__ float softplus_fast(float v) {
+    const float L2E = 1.44269502162933349609375f, L2E_LO = 1.925963033500414e-08f, LN2 = 0.693147182464599609375f;
+    const float hi = v * L2E;
+    const float lo = __builtin_fmaf(v, L2E, -hi) + v * L2E_LO;
+    float e = __builtin_amdgcn_exp2f(hi);
+    e = __builtin_fmaf(e, lo * LN2, e);
+    const float w = 1.f + e, d = w - 1.f;
+    const float r = (__builtin_amdgcn_logf(w) * LN2) * (e * __builtin_amdgcn_rcpf(d));
+    const float sp = d == 0.f ? e : r;
+    return v > 20.f ? v : sp;
+}
+
+// its derivative from the same e: sigmoid(v) = e / (1 + e), 1 above softplus's threshold (where softplus is the identity)
+__device__ __forceinline__ float sigmoid_fast(float v) {
+    const float L2E = 1.44269502162933349609375f, L2E_LO = 1.925963033500414e-08f, LN2 = 0.693147182464599609375f;
+    const float hi = v * L2E;
+    const float lo = __builtin_fmaf(v, L2E, -hi) + v * L2E_LO;
+    float e = __builtin_amdgcn_exp2f(hi);
+    e = __builtin_fmaf(e, lo * LN2, e);
+    return v > 20.f ? 1.f : e * __builtin_amdgcn_rcpf(1.f + e);
+}
+
 // ---- FOV warp of the alignment network (End_to_End.py:106-134), shared by fov_warp_kernel, flow_volume_kernel and conv_tile's
 // warp-fill variant -------------------------------------------------------------------------------------------------------
 // flow of grid point (xx,yy) of a slice with scale f = FOV + a0 and shifts a1, a2, and the un-normalised sample

@@ -113,6 +113,11 @@ def _load():
     lib.dffw_sim_plan_host.argtypes = [POINTER(SimParams), POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, c_int,
                                        POINTER(ctypes.c_double), POINTER(c_int), POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int)]
     lib.dffw_sim_disk_rows.argtypes = [c_int, POINTER(c_int)]
+    lib.dffw_loss_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.dffw_loss_workspace_bytes.restype = c_int64
+    lib.dffw_loss_heads.argtypes = [c_int, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int64),
+                                    c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_float, c_float, POINTER(c_void_p), POINTER(c_void_p),
+                                    c_void_p, c_void_p, c_int64, c_void_p]
     return lib
 
 
@@ -132,6 +137,7 @@ ABI_SYMBOLS = (
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
     "dffw_sim_workspace_bytes", "dffw_sim_render", "dffw_sim_plan_host", "dffw_sim_disk_rows",
+    "dffw_loss_workspace_bytes", "dffw_loss_heads",
 )
 
 
@@ -475,6 +481,52 @@ def op_regress(score, focus_dists, H, W):
                                    (c_int64 * 4)(*fd.stride()), c_void_p(depth.data_ptr()), _stream_ptr(dev)),
                "dffw_op_regress")
     return depth
+
+
+def loss_workspace_bytes(B, N, H, W):
+    return int(lib.dffw_loss_workspace_bytes(B, N, H, W))
+
+
+def op_loss_heads(scores, focus_dists, gt, mask, conf=None, weights=(0.3, 0.5, 0.7, 1.0), depth_range=None, *, preds=True, grads=True,
+                  workspace=None):
+    """dffw_loss_heads: the training scripts' loss over 1..4 regression heads and its gradient down to the score volumes.
+    scores: fp32 (B,N,h_k,w_k) CUDA tensors; focus_dists broadcastable to (B,N,H,W); gt fp32 (B,H,W); mask uint8 (B,H,W); conf fp32 (B,H,W)
+    or None; depth_range (lo, hi) or None.  preds / grads: False skips those outputs (NULL in the C ABI).  workspace: uint8 tensor of at least
+    loss_workspace_bytes(B,N,H,W) (allocated when None; it need not be cleared).
+    Returns (losses fp64 (n_heads+1: per head, then the weighted total), [pred_k (B,H,W)] or None, [grad_k like scores[k]] or None)."""
+    n = len(scores)
+    B, H, W = gt.shape
+    N = scores[0].shape[1]
+    dev = scores[0].device.index if scores[0].device.index is not None else torch.cuda.current_device()
+    device = scores[0].device
+    scores = [s.contiguous() for s in scores]
+    for s in scores:
+        if s.dtype != torch.float32 or s.dim() != 4 or s.shape[0] != B or s.shape[1] != N:
+            raise ValueError(f"score volumes must be float32 (B,N,h,w) with B={B}, N={N}; got {s.dtype} {tuple(s.shape)}")
+    gt, mask = gt.contiguous(), mask.contiguous()
+    if gt.dtype != torch.float32 or mask.dtype != torch.uint8 or tuple(mask.shape) != (B, H, W):
+        raise ValueError("gt must be float32 (B,H,W) and mask uint8 of the same shape")
+    if conf is not None:
+        conf = conf.contiguous()
+        if conf.dtype != torch.float32 or tuple(conf.shape) != (B, H, W):
+            raise ValueError("conf must be float32 (B,H,W)")
+    if len(weights) < n:
+        raise ValueError(f"{n} heads but {len(weights)} weights")
+    fd = focus_dists.expand(B, N, H, W)
+    pred = [torch.empty((B, H, W), dtype=torch.float32, device=device) for _ in range(n)] if preds else None
+    grad = [torch.empty_like(s) for s in scores] if grads else None
+    losses = torch.empty(n + 1, dtype=torch.float64, device=device)
+    need = loss_workspace_bytes(B, N, H, W)
+    ws = workspace if workspace is not None else torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    ptrs = lambda ts: (c_void_p * 4)(*[t.data_ptr() for t in ts]) if ts is not None else None
+    lo, hi = (0.0, 1.0) if depth_range is None else (float(depth_range[0]), float(depth_range[1]))
+    with torch.cuda.device(dev):
+        _check(lib.dffw_loss_heads(dev, n, ptrs(scores), (c_int * 4)(*[s.shape[2] for s in scores]), (c_int * 4)(*[s.shape[3] for s in scores]),
+                                   B, N, H, W, c_void_p(fd.data_ptr()), (c_int64 * 4)(*fd.stride()), c_void_p(gt.data_ptr()), c_void_p(mask.data_ptr()),
+                                   c_void_p(conf.data_ptr()) if conf is not None else None, (c_float * 4)(*[float(x) for x in weights[:n]]),
+                                   0 if depth_range is None else 1, lo, hi, ptrs(pred), ptrs(grad), c_void_p(losses.data_ptr()),
+                                   c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(dev)), "dffw_loss_heads")
+    return losses, pred, grad
 
 
 def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False):

@@ -288,3 +288,46 @@ def masked_metrics(est, gt, mask, conf=None):
                                 c_void_p(conf.data_ptr()) if conf is not None else None, h, w, c_void_p(out.data_ptr()),
                                 c_void_p(scratch.data_ptr()), nbytes, _stream_ptr(dev)), "dffw_metrics")
     return out
+
+
+# ---- training loss and regression-head backward (first link) ---------------------------------------------
+HEAD_WEIGHTS = (0.3, 0.5, 0.7, 1.0)   # mid_out, pred1, pred2, pred3: train_code_*.py
+
+
+def _loss_mask(mask):
+    if mask.dtype == torch.bool:
+        return mask.contiguous().view(torch.uint8)
+    if mask.dtype != torch.uint8:
+        raise ValueError(f"mask must be bool or uint8, got {mask.dtype}")
+    return mask
+
+
+def training_loss(scores, focus_dists, gt, mask, conf=None, weights=HEAD_WEIGHTS, depth_range=None, grads=True):
+    """The loss of the reference's training scripts on the four score volumes (conf, cost1, cost2, cost3 of the forward's taps), and its
+    gradient with respect to them:
+
+        Loss_k = sum(conf * ((d_k - gt)/r)^2 over mask) / sum(conf over mask),   total = sum_k weights[k] * Loss_k
+
+    with d_k the k-th regression head's depth map, r = hi - lo of depth_range (FlyingThings (10, 100), Smartphone (1/3.91092, 1/0.10201))
+    or 1, conf = 1 when None (then Loss_k is nn.MSELoss over est[mask]).  mask: bool or uint8.  An empty mask gives NaN losses and zero
+    gradients, as torch does on an empty selection.  Returns (total, per_head, preds, grads): float64 scalar, float64 (len(scores),),
+    list of (B,H,W) depth maps, list of gradients shaped like the scores (None with grads=False).  All device tensors; nothing syncs."""
+    _dev(scores[0], "score volumes")
+    losses, preds, g = engine.op_loss_heads(list(scores), focus_dists.float(), gt, _loss_mask(mask), conf, weights, depth_range, grads=grads)
+    return losses[-1], losses[:-1], preds, g
+
+
+class HeadsLoss(torch.autograd.Function):
+    """total = HeadsLoss.apply(conf_score, cost1, cost2, cost3, focus_dists, gt, mask, conf, weights, depth_range): the total training loss
+    (float32 scalar) as an autograd node, so that any PyTorch producer of the four score volumes trains against the HIP heads.  The gradients
+    are computed in the forward launch and scaled by the incoming gradient in backward; the non-score arguments get None."""
+
+    @staticmethod
+    def forward(ctx, s0, s1, s2, s3, focus_dists, gt, mask, conf=None, weights=HEAD_WEIGHTS, depth_range=None):
+        total, _, _, g = training_loss([s0.detach(), s1.detach(), s2.detach(), s3.detach()], focus_dists, gt, mask, conf, weights, depth_range)
+        ctx.save_for_backward(*g)
+        return total.float()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return tuple(g * grad_out for g in ctx.saved_tensors) + (None,) * 6

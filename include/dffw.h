@@ -301,6 +301,29 @@ int64_t dffw_metrics_scratch_bytes(int B);
 int dffw_metrics(int device, const float *est, int B, int H, int W, const float *gt, const uint8_t *mask,
                  const float *conf, int h, int w, double *out, void *scratch, int64_t scratch_bytes, void *hip_stream);
 
+/* ---- training loss and regression-head backward (train_codes/train_code_*.py, Depth_Estimation_Network.py:89-98, 118-134) ----
+ * dffw_loss_heads evaluates, for n_heads regression heads that share the output size, the focus distances and the ground truth,
+ *     d_k    = the head's prediction (bit-identical to dffw_op_regress on the same scores)
+ *     Loss_k = sum_i c_i m_i ((d_k - gt)/r)^2 / Z,  Z = sum_i c_i m_i   (c = 1 without conf: nn.MSELoss over est[mask]),  r = hi - lo or 1
+ *     Total  = sum_k weights[k] Loss_k
+ * and dTotal/dscore_k, the gradient through softplus, the normalisation over the slices and the bilinear upsample.
+ *   score[k]      device fp32 (B,N,h[k],w[k]); H = s*h[k], W = s*w[k] with s in {1,2,4,8} (else DFFW_EINVAL)
+ *   focus_dists   device fp32, element strides fd_strides (any, 0 included) for dims (B,N,H,W)
+ *   gt, conf      device fp32 (B,H,W), conf may be NULL; mask uint8 (B,H,W), non-zero = valid.  A pixel outside the mask
+ *                 contributes nothing, whatever its gt (NaN included)
+ *   pred[k]       device fp32 (B,H,W), entries or the array may be NULL
+ *   grad[k]       device fp32 (B,N,h[k],w[k]), entries or the array may be NULL (loss only)
+ *   losses        device fp64, n_heads + 1: Loss_k per head, then Total.  Z == 0: NaN losses and all-zero gradients
+ *   workspace     device memory of dffw_loss_workspace_bytes(B,N,H,W): Z and the workgroups' float64 loss partials; need not be cleared
+ * Enqueue-only on hip_stream, no allocation; float64 sums and the gather-form upsample adjoint run in a fixed order (no atomics), so
+ * two calls give identical bits.  B <= 65535, H*W < 2^31; B*H*W and N are free.  dffw_last_op_kernels lists the launches. */
+int64_t dffw_loss_workspace_bytes(int B, int N, int H, int W);
+int dffw_loss_heads(int device, int n_heads, const float *const score[4], const int h[4], const int w[4],
+                    int B, int N, int H, int W, const float *focus_dists, const int64_t fd_strides[4],
+                    const float *gt, const uint8_t *mask, const float *conf, const float weights[4],
+                    int use_range, float lo, float hi, float *const pred[4], float *const grad[4],
+                    double *losses, void *workspace, int64_t workspace_bytes, void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

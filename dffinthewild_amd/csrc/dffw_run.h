@@ -184,6 +184,10 @@ enum SwitchId {
     X(ROLL_MIN_UNITS, roll_min_units, 1, 192)                                                                                                              \
     /* measured best of 64/128/256/512 at batch 1, 4, 8 */                                                                                                 \
     X(SPLIT_WG, split_wg, INT_MIN, 256)                                                                                                                    \
+    /* the weight-gradient kernel: workgroups of a launch over grid.x * grid.y (0: its default), and the units a workgroup's fp32          \
+       accumulators sum before they are flushed (tests lower both so that one workgroup walks many units and flushes more than once) */                    \
+    X(WGRAD_WGS, wgrad_wgs, 8, 0)                                                                                                                          \
+    X(WGRAD_FLUSH_UNITS, wgrad_flush_units, 1, 256)                                                                                                        \
     X(DEBUG_FLAGS, debug_flags, INT_MIN, 0)
 // ... and the two 64-bit ones (any atoll() result is taken): X(variable, field, default)
 #define DFFW_INT64_KNOBS(X)                                                                                                                                \

@@ -118,6 +118,12 @@ def _load():
     lib.dffw_loss_heads.argtypes = [c_int, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int64),
                                     c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_float, c_float, POINTER(c_void_p), POINTER(c_void_p),
                                     c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_op_conv3d_backward.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int,
+                                            POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.dffw_conv_wgrad_workspace_bytes.argtypes = [c_int] * 6 + [POINTER(c_int)] * 3 + [c_int]
+    lib.dffw_conv_wgrad_workspace_bytes.restype = c_int64
+    lib.dffw_conv_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                    POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_int64, c_void_p]
     return lib
 
 
@@ -138,6 +144,7 @@ ABI_SYMBOLS = (
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
     "dffw_sim_workspace_bytes", "dffw_sim_render", "dffw_sim_plan_host", "dffw_sim_disk_rows",
     "dffw_loss_workspace_bytes", "dffw_loss_heads",
+    "dffw_op_conv3d_backward", "dffw_conv_wgrad_workspace_bytes", "dffw_conv_wgrad",
 )
 
 
@@ -384,6 +391,52 @@ def op_conv3d(x, weight, *, stride=1, pad=0, dilation=1, transposed=False, bn=No
             return y, y_pre, score
         _check(lib.dffw_op_conv3d(*args, _stream_ptr(dev)), "dffw_op_conv3d")
     return y
+
+
+def conv3d_output_shape(x_shape, weight_shape, stride, pad, transposed):
+    """Shape of conv(x, weight) for the plain convs of op_conv3d_backward (dilation 1; the transposed form has output_padding (0,1,1))."""
+    B, Cin, N, H, W = x_shape
+    k, s, p = tuple(weight_shape[2:]), tuple(_i3(stride)), tuple(_i3(pad))
+    if transposed:
+        return (B, weight_shape[1], N, 2 * H, 2 * W)
+    return (B, weight_shape[0], N + 2 * p[0] - (k[0] - 1), (H + 2 * p[1] - k[1]) // s[1] + 1, (W + 2 * p[2] - k[2]) // s[2] + 1)
+
+
+def op_conv3d_backward(x, weight, grad_y, *, stride=1, pad=0, dilation=1, transposed=False, precision="bf16x3", need=("x", "w")):
+    """(grad_x, grad_w) of <grad_y, conv(x, weight)> for the plain convs of the aggregation network (dffw_op_conv3d_backward: 3x3x3 and 1x3x3
+    stride 1, 3x3x3 stride (1,2,2), the transposed 3x3x3; no BN, bias, ReLU or residual).  ``x`` (B,Cin,N,H,W) and ``grad_y`` float32 on the
+    GPU, ``weight`` CPU/GPU float32 in PyTorch layout.  ``need``: which of "x", "w" to compute; the other entry is None.  grad_x comes from the
+    adjoint conv through the forward's dispatch, grad_w from the conv_wgrad kernels; both are float32 GPU tensors."""
+    if x.device.type != "cuda" or grad_y.device.type != "cuda":
+        raise DffwError("op_conv3d_backward needs GPU tensors (no CPU fallback)")
+    if tuple(_i3(dilation)) != (1, 1, 1):
+        raise ValueError(f"op_conv3d_backward: dilation must be 1, got {dilation}")
+    if x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5:
+        raise ValueError("op_conv3d_backward: x, weight and grad_y must have 5 dimensions")
+    B, Cin, N, H, W = x.shape
+    if weight.shape[1 if not transposed else 0] != Cin:
+        raise ValueError(f"op_conv3d_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
+    Cout = weight.shape[1] if transposed else weight.shape[0]
+    k = tuple(weight.shape[2:])
+    s, p = _i3(stride), _i3(pad)
+    w = weight.detach().to("cpu", torch.float32).contiguous()
+    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    gx = torch.empty_like(x) if "x" in need else None
+    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
+
+    def call(with_x, with_w):
+        return lib.dffw_op_conv3d_backward(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), s, p,
+                                           int(transposed), c_void_p(grad_y.data_ptr()), c_void_p(gx.data_ptr()) if with_x else None,
+                                           c_void_p(gw.data_ptr()) if with_w else None, _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        # the C entry point takes grad_y's shape from the geometry: its own refusals first (a call with no output launches nothing), then the tensor
+        _check(call(False, False), "dffw_op_conv3d_backward")
+        want = conv3d_output_shape(x.shape, w.shape, stride, pad, transposed)
+        if tuple(grad_y.shape) != want:
+            raise ValueError(f"op_conv3d_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
+        _check(call(gx is not None, gw is not None), "dffw_op_conv3d_backward")
+    return gx, gw
 
 
 def probe_peaks(device=0):

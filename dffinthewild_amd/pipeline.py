@@ -331,3 +331,33 @@ class HeadsLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return tuple(g * grad_out for g in ctx.saved_tensors) + (None,) * 6
+
+
+# ---- conv backward: one plain conv of the aggregation network as an autograd node ----------------------------------------
+class Conv3d(torch.autograd.Function):
+    """y = Conv3d.apply(x, weight, stride, pad, transposed, precision): the plain conv (no BN, bias or ReLU) through engine.op_conv3d, its
+    backward through engine.op_conv3d_backward (the adjoint conv on the forward's dispatch for x, the conv_wgrad kernels for the weight)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride=1, pad=0, transposed=False, precision="bf16x3"):
+        _dev(x, "x")
+        ctx.save_for_backward(x, weight)
+        ctx.geom = (stride, pad, transposed, precision)
+        return engine.op_conv3d(x.detach().float(), weight, stride=stride, pad=pad, transposed=transposed, precision=precision)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        stride, pad, transposed, precision = ctx.geom
+        need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
+        gx, gw = engine.op_conv3d_backward(x, weight, grad_y, stride=stride, pad=pad, transposed=transposed, precision=precision, need=need)
+        if gw is not None:
+            gw = gw.to(weight.device, weight.dtype)
+        return gx, gw, None, None, None, None
+
+
+def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
+    """conv(x, weight) on the HIP kernels with gradients for both: x (B,Cin,N,H,W) float32 CUDA, weight in PyTorch layout (CPU or CUDA).  The
+    geometries are those of engine.op_conv3d_backward, channels multiples of 8 up to 128.  With training_loss / HeadsLoss behind it a score
+    volume's gradient flows one layer further in the caller's autograd graph."""
+    return Conv3d.apply(x, weight, stride, pad, transposed, precision)

@@ -324,6 +324,33 @@ int dffw_loss_heads(int device, int n_heads, const float *const score[4], const 
                     int use_range, float lo, float hi, float *const pred[4], float *const grad[4],
                     double *losses, void *workspace, int64_t workspace_bytes, void *hip_stream);
 
+/* ---- conv backward: data and weight gradients of the aggregation network's plain convs ------------------------------
+ * Geometries (anything else, and dilation, is DFFW_EINVAL): 3x3x3 pad 1 stride 1 or (1,2,2); 1x3x3 pad (0,1,1) stride 1; the transposed
+ * 3x3x3 stride (1,2,2) pad 1 output_padding (0,1,1).  Cin and Cout multiples of 8, at most 128; H and W even at stride (1,2,2).
+ *   grad_x = d<grad_y, conv(x, weight)>/dx   the adjoint conv, through the forward's own kernel dispatch (dffw_last_conv_kernel shows it)
+ *   grad_w = d<grad_y, conv(x, weight)>/dw   dffw::conv_wgrad_kernel + dffw::conv_wgrad_finish_kernel (dffw_last_op_kernels lists them)
+ * in the engine's arithmetic: both operands rounded to the activation records of `precision`, fp32 MFMA accumulation; the weight gradient's
+ * fp32 accumulators are flushed into float64 sums after at most 16 384 pixels, and those are added in a fixed order (no atomics: two calls
+ * give identical bits).
+ *
+ * dffw_op_conv3d_backward: layouts as dffw_op_conv3d.  x (B,Cin,N,H,W) and grad_y (the forward's output shape: (B,Cout,N,H/s,W/s), or
+ * (B,Cout,N,2H,2W) transposed) device fp32; weight host fp32 in PyTorch layout (may be NULL without grad_x); grad_x device fp32 like x, or
+ * NULL; grad_w DEVICE fp32 in the weight's PyTorch layout, or NULL.  No BatchNorm, bias, ReLU or residual: the plain conv's adjoint.
+ * Allocates its temporaries, poisons its workspace with 0xFF and synchronises.  grad_y's shape is implied by the geometry (the Python
+ * binding checks the tensor against it).
+ *
+ * dffw_conv_wgrad: the enqueue-only form a training step calls.  x and grad_y are activation RECORDS [pixel][part][channel] (16-bit, the
+ * engine's internal layout) of the same shapes; workspace: dffw_conv_wgrad_workspace_bytes(...) bytes, need not be cleared (0 for
+ * arguments dffw_conv_wgrad refuses). */
+int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight, int Cout,
+                            const int kernel[3], const int stride[3], const int pad[3], int transposed, const float *grad_y, float *grad_x,
+                            float *grad_w, void *hip_stream);
+int64_t dffw_conv_wgrad_workspace_bytes(int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int stride[3],
+                                        const int pad[3], int transposed);
+int dffw_conv_wgrad(int device, int precision, const void *x, int B, int Cin, int N, int H, int W, const void *grad_y, int Cout,
+                    const int kernel[3], const int stride[3], const int pad[3], int transposed, float *grad_w, void *workspace,
+                    int64_t workspace_bytes, void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

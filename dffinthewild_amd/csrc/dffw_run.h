@@ -188,6 +188,9 @@ enum SwitchId {
        accumulators sum before they are flushed (tests lower both so that one workgroup walks many units and flushes more than once) */                    \
     X(WGRAD_WGS, wgrad_wgs, 8, 0)                                                                                                                          \
     X(WGRAD_FLUSH_UNITS, wgrad_flush_units, 1, 256)                                                                                                        \
+    /* train-mode BatchNorm: workgroups of each of its streaming launches (0: its default; below 8: 8, one per XCD).  Changes only the     \
+       order of the float64 additions */                                                                                                                   \
+    X(BN_WGS, bn_wgs, 1, 0)                                                                                                                                \
     X(DEBUG_FLAGS, debug_flags, INT_MIN, 0)
 // ... and the two 64-bit ones (any atoll() result is taken): X(variable, field, default)
 #define DFFW_INT64_KNOBS(X)                                                                                                                                \

@@ -124,6 +124,15 @@ def _load():
     lib.dffw_conv_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_conv_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    c_double = ctypes.c_double
+    lib.dffw_bn_train_workspace_bytes.argtypes = [c_int] * 5
+    lib.dffw_bn_train_workspace_bytes.restype = c_int64
+    lib.dffw_bn_train_forward.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 3 + \
+                                         [c_int] + [c_void_p] * 4 + [c_int64, c_void_p]
+    lib.dffw_bn_train_backward.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_int64, c_void_p]
+    lib.dffw_op_bn_train.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 3 + \
+                                    [c_int] + [c_void_p] * 4
+    lib.dffw_op_bn_train_backward.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_int] + [c_void_p] * 5
     return lib
 
 
@@ -145,6 +154,7 @@ ABI_SYMBOLS = (
     "dffw_sim_workspace_bytes", "dffw_sim_render", "dffw_sim_plan_host", "dffw_sim_disk_rows",
     "dffw_loss_workspace_bytes", "dffw_loss_heads",
     "dffw_op_conv3d_backward", "dffw_conv_wgrad_workspace_bytes", "dffw_conv_wgrad",
+    "dffw_bn_train_workspace_bytes", "dffw_bn_train_forward", "dffw_bn_train_backward", "dffw_op_bn_train", "dffw_op_bn_train_backward",
 )
 
 
@@ -437,6 +447,73 @@ def op_conv3d_backward(x, weight, grad_y, *, stride=1, pad=0, dilation=1, transp
             raise ValueError(f"op_conv3d_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
         _check(call(gx is not None, gw is not None), "dffw_op_conv3d_backward")
     return gx, gw
+
+
+BN_EPS = 1e-5   # nn.BatchNorm3d's default, the value every BatchNorm of the reference network has
+
+
+def _bn_vec(t, C, dev, what):
+    if t.device.type != "cuda":
+        raise DffwError(f"{what} must be a GPU tensor (no CPU fallback)")
+    if t.numel() != C:
+        raise ValueError(f"{what} holds {t.numel()} values, the tensor has {C} channels")
+    return t.detach().to(dev, torch.float32).contiguous()
+
+
+def op_bn_train(x, gamma, beta, running_mean=None, running_var=None, *, residual=None, relu=False, eps=BN_EPS, momentum=0.1, precision="bf16x3"):
+    """Train-mode BatchNorm3d (dffw_op_bn_train): ``y = [relu](gamma (x - mean) invstd + beta [+ residual])`` with the batch
+    statistics of ``x`` (B,C,N,H,W) float32 on the GPU, C in {8, 16, 32, 64, 128}.  Returns (y, save_mean, save_invstd); ``running_mean`` /
+    ``running_var`` (float32 GPU tensors of C values) are updated in place with ``momentum`` (unbiased variance), as nn.BatchNorm3d does."""
+    tensors = [x, gamma, beta] + [t for t in (running_mean, running_var, residual) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_bn_train needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5:
+        raise ValueError("op_bn_train: x must have 5 dimensions")
+    B, C, N, H, W = x.shape
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError(f"op_bn_train: residual {tuple(residual.shape)} is not x's shape {tuple(x.shape)}")
+    for t in (running_mean, running_var):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C and t.device == x.device):
+            raise ValueError("op_bn_train: the running statistics must be contiguous float32 tensors of C values on x's device (they are updated in place)")
+    x = x.detach().float().contiguous()
+    res = residual.detach().float().contiguous() if residual is not None else None
+    g, b = _bn_vec(gamma, C, x.device, "gamma"), _bn_vec(beta, C, x.device, "beta")
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    y = torch.empty_like(x)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_bn_train(dev, PRECISIONS[precision], ptr(x), B, C, N, H, W, ptr(g), ptr(b), float(eps), float(momentum), ptr(running_mean),
+                                    ptr(running_var), ptr(res), int(bool(relu)), ptr(y), ptr(mean), ptr(invstd), _stream_ptr(dev)), "dffw_op_bn_train")
+    return y, mean, invstd
+
+
+def op_bn_train_backward(x, y, grad_y, gamma, save_mean, save_invstd, *, relu=False, residual=False, precision="bf16x3", need=("x", "params")):
+    """Backward of op_bn_train (dffw_op_bn_train_backward): returns (grad_x, grad_res or None, grad_gamma, grad_beta).  ``y`` is the forward's
+    output (the ReLU mask is ``y > 0``; may be None without ReLU), ``residual``: whether a residual was added (grad_res is then the masked grad_y).
+    ``need`` without "x": only the parameter gradients are computed (grad_x and grad_res come back None); they are always computed."""
+    tensors = [x, grad_y, gamma, save_mean, save_invstd] + ([y] if y is not None else [])
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_bn_train_backward needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5 or grad_y.shape != x.shape or (y is not None and y.shape != x.shape):
+        raise ValueError("op_bn_train_backward: x, y and grad_y must be 5-dimensional tensors of one shape")
+    if relu and y is None:
+        raise ValueError("op_bn_train_backward: the ReLU mask is read from y")
+    B, C, N, H, W = x.shape
+    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
+    y = y.detach().float().contiguous() if relu else None
+    g, mean, invstd = (_bn_vec(t, C, x.device, n) for t, n in ((gamma, "gamma"), (save_mean, "save_mean"), (save_invstd, "save_invstd")))
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    gx = torch.empty_like(x) if "x" in need else None
+    gres = torch.empty_like(x) if residual and gx is not None else None
+    gg = torch.empty(C, dtype=torch.float32, device=x.device)
+    gb = torch.empty_like(gg)
+    ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_bn_train_backward(dev, PRECISIONS[precision], ptr(x), ptr(y), ptr(grad_y), B, C, N, H, W, ptr(g), ptr(mean), ptr(invstd),
+                                             int(bool(relu)), ptr(gx), ptr(gres), ptr(gg), ptr(gb), _stream_ptr(dev)), "dffw_op_bn_train_backward")
+    return gx, gres, gg, gb
 
 
 def probe_peaks(device=0):

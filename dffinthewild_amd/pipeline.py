@@ -361,3 +361,37 @@ def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
     geometries are those of engine.op_conv3d_backward, channels multiples of 8 up to 128.  With training_loss / HeadsLoss behind it a score
     volume's gradient flows one layer further in the caller's autograd graph."""
     return Conv3d.apply(x, weight, stride, pad, transposed, precision)
+
+
+# ---- train-mode BatchNorm (DESIGN.md section 14): BatchNorm3d with its residual add and ReLU as an autograd node -------------------------------
+class BatchNorm3d(torch.autograd.Function):
+    """y = BatchNorm3d.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, precision): nn.BatchNorm3d in training
+    mode followed by the optional residual add and ReLU, through engine.op_bn_train; the backward through engine.op_bn_train_backward gives the
+    gradients of x, gamma, beta and the residual.  The running statistics are updated in place by the forward."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean=None, running_var=None, residual=None, relu=False, eps=engine.BN_EPS, momentum=0.1, precision="bf16x3"):
+        _dev(x, "x")
+        y, mean, invstd = engine.op_bn_train(x, gamma, beta, running_mean, running_var, residual=residual, relu=relu, eps=eps, momentum=momentum,
+                                             precision=precision)
+        ctx.save_for_backward(x, y, gamma, mean, invstd)
+        ctx.cfg = (bool(relu), residual is not None, precision)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, y, gamma, mean, invstd = ctx.saved_tensors
+        relu, has_res, precision = ctx.cfg
+        need_x = ctx.needs_input_grad[0] or (has_res and ctx.needs_input_grad[5])
+        gx, gres, gg, gb = engine.op_bn_train_backward(x, y, grad_y, gamma, mean, invstd, relu=relu, residual=has_res and ctx.needs_input_grad[5],
+                                                       precision=precision, need=("x", "params") if need_x else ("params",))
+        return (gx if ctx.needs_input_grad[0] else None, gg.to(gamma.dtype) if ctx.needs_input_grad[1] else None,
+                gb.to(gamma.dtype) if ctx.needs_input_grad[2] else None, None, None, gres, None, None, None, None)
+
+
+def batch_norm3d(x, gamma, beta, running_mean=None, running_var=None, *, residual=None, relu=False, eps=engine.BN_EPS, momentum=0.1,
+                 precision="bf16x3"):
+    """[relu](BatchNorm3d(x) [+ residual]) in training mode on the HIP kernels, with gradients for x, gamma, beta and the residual: x (B,C,N,H,W)
+    float32 CUDA with 8, 16, 32, 64 or 128 channels, gamma / beta / the running statistics CUDA tensors of C values (the running statistics
+    float32, updated in place).  Behind pipeline.conv3d this is one conv -> BN -> (+skip) -> ReLU layer of the aggregation network."""
+    return BatchNorm3d.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, precision)

@@ -335,7 +335,8 @@ int dffw_loss_heads(int device, int n_heads, const float *const score[4], const 
  *
  * dffw_op_conv3d_backward: layouts as dffw_op_conv3d.  x (B,Cin,N,H,W) and grad_y (the forward's output shape: (B,Cout,N,H/s,W/s), or
  * (B,Cout,N,2H,2W) transposed) device fp32; weight host fp32 in PyTorch layout (may be NULL without grad_x); grad_x device fp32 like x, or
- * NULL; grad_w DEVICE fp32 in the weight's PyTorch layout, or NULL.  No BatchNorm, bias, ReLU or residual: the plain conv's adjoint.
+ * NULL; grad_w DEVICE fp32 in the weight's PyTorch layout, or NULL.  No bias: the plain conv's adjoint (train-mode BatchNorm with its ReLU
+ * and residual gradients is dffw_bn_train_backward below).
  * Allocates its temporaries, poisons its workspace with 0xFF and synchronises.  grad_y's shape is implied by the geometry (the Python
  * binding checks the tensor against it).
  *
@@ -350,6 +351,41 @@ int64_t dffw_conv_wgrad_workspace_bytes(int B, int Cin, int N, int H, int W, int
 int dffw_conv_wgrad(int device, int precision, const void *x, int B, int Cin, int N, int H, int W, const void *grad_y, int Cout,
                     const int kernel[3], const int stride[3], const int pad[3], int transposed, float *grad_w, void *workspace,
                     int64_t workspace_bytes, void *hip_stream);
+
+/* ---- train-mode BatchNorm3d with its residual add and ReLU, forward and backward -------------------------------------
+ * Per channel c over the M = B*N*H*W pixels of a volume (nn.BatchNorm3d in training mode, Depth_Estimation_Network.py convbn_3d):
+ *     mean = sum x / M    var = sum (x - mean)^2 / M (biased)    invstd = 1 / sqrt(var + eps)
+ *     y = [relu]( gamma (x - mean) invstd + beta [+ res] )
+ *     running_mean <- (1 - momentum) running_mean + momentum mean      running_var <- ... + momentum var M / (M - 1)
+ *     g = relu ? grad_y [y > 0] : grad_y     grad_res = g     grad_beta = sum g     grad_gamma = sum g (x - mean) invstd
+ *     grad_x = gamma invstd ( g - grad_beta / M - (x - mean) invstd grad_gamma / M )
+ * x is the value the records hold (hi + lo for split-bf16).  The sums are float64 sums of exact terms, per workgroup and then over the
+ * workgroups in a fixed order (no atomics): two calls give identical bits; DFFW_BN_WGS (the launches' workgroups) changes only the
+ * order of float64 additions.  Refused with DFFW_EINVAL before any launch: C outside {8, 16, 32, 64, 128}, M == 1 (PyTorch raises
+ * there), M >= 2^31, eps <= 0, an unknown precision; a short workspace is DFFW_ENOMEM.  dffw_last_op_kernels lists the launches.
+ *
+ * Record forms (dffw_bn_train_forward / _backward): enqueue-only on hip_stream, no allocation.  x, res, y, grad_y, grad_x, grad_res
+ * are activation RECORDS [pixel][part][channel] of `precision` (16-byte aligned), the layout dffw_conv_wgrad reads; gamma, beta,
+ * running_*, save_*, grad_gamma, grad_beta device fp32 (C).  May be NULL: running_mean, running_var, res, grad_res; y in the forward
+ * without ReLU and residual (statistics only) and in the backward without ReLU; grad_x (parameter gradients only; then grad_res too).
+ * The ReLU mask of the backward is read from the stored y.  workspace: dffw_bn_train_workspace_bytes(...) bytes (0 for a refused
+ * shape): the workgroups' float64 partial sums, nothing that scales with M; need not be cleared.
+ *
+ * Op forms (dffw_op_bn_train / _backward): the same on device fp32 tensors (B,C,N,H,W); they convert to records and back, allocate
+ * their temporaries, poison the workspace with 0xFF and synchronise.  y of the backward is the forward's returned y. */
+int64_t dffw_bn_train_workspace_bytes(int B, int C, int N, int H, int W);
+int dffw_bn_train_forward(int device, int precision, const void *x, int B, int C, int N, int H, int W, const float *gamma, const float *beta,
+                          double eps, double momentum, float *running_mean, float *running_var, const void *res, int relu, void *y,
+                          float *save_mean, float *save_invstd, void *workspace, int64_t workspace_bytes, void *hip_stream);
+int dffw_bn_train_backward(int device, int precision, const void *x, const void *y, const void *grad_y, int B, int C, int N, int H, int W,
+                           const float *gamma, const float *save_mean, const float *save_invstd, int relu, void *grad_x, void *grad_res,
+                           float *grad_gamma, float *grad_beta, void *workspace, int64_t workspace_bytes, void *hip_stream);
+int dffw_op_bn_train(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *gamma, const float *beta,
+                     double eps, double momentum, float *running_mean, float *running_var, const float *res, int relu, float *y,
+                     float *save_mean, float *save_invstd, void *hip_stream);
+int dffw_op_bn_train_backward(int device, int precision, const float *x, const float *y, const float *grad_y, int B, int C, int N, int H,
+                              int W, const float *gamma, const float *save_mean, const float *save_invstd, int relu, float *grad_x,
+                              float *grad_res, float *grad_gamma, float *grad_beta, void *hip_stream);
 
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D

@@ -1,5 +1,5 @@
 // Train-mode BatchNorm3d: the C ABI of the kernels of dffw_bn.hip.  The record forms enqueue on the caller's stream into the caller's
-// workspace; the op forms convert fp32 NCDHW tensors with the from_ncdhw / to_ncdhw kernels around them, as dffw_op_conv3d_backward does.
+// workspace; the op forms (dffw_ops.cpp) convert fp32 NCDHW tensors with the from_ncdhw / to_ncdhw kernels around them.
 #include <string>
 
 #include "dffw_bn.h"
@@ -37,6 +37,11 @@ BnArgs base_args(const void *x, int C, int M, void *workspace) {
 }
 
 }  // namespace
+
+int dffw::bn_train_check(int precision, int B, int C, int N, int H, int W) {
+    int M;
+    return check_shape(precision, B, C, N, H, W, &M);
+}
 
 extern "C" {
 
@@ -112,74 +117,6 @@ int dffw_bn_train_backward(int device, int precision, const void *x, const void 
     }
     dffw_set_last_op_kernels(names.c_str());
     return DFFW_OK;
-}
-
-int dffw_op_bn_train(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *gamma, const float *beta, double eps,
-                     double momentum, float *running_mean, float *running_var, const float *res, int relu, float *y, float *save_mean,
-                     float *save_invstd, void *hip_stream) {
-    dffw_set_last_op_kernels("");
-    int M;
-    if (int rc = check_shape(precision, B, C, N, H, W, &M)) return rc;
-    if (!(eps > 0.0)) return fail(DFFW_EINVAL, "eps must be positive, got %g", eps);
-    if (!x || !gamma || !beta || !y || !save_mean || !save_invstd) return fail(DFFW_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    const int64_t rb = ((int64_t)M * prec_parts(precision) * C * 2 + 255) & ~(int64_t)255;
-    const int64_t wsb = workspace_bytes(M, C, Switches::read());
-    const int64_t xo = 0, ro = rb, yo = 2 * rb, wo = 3 * rb, total = wo + wsb;
-    char *buf = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, total));
-    // poisoned (NaN in every format): a record no kernel stores, or a partial read before it is written, shows
-    hipError_t h = hipMemsetAsync(buf, 0xFF, total, s);
-    if (h == hipSuccess) h = launch_from_ncdhw(precision, x, (uint16_t *)(buf + xo), B, C, N, H, W, s);
-    if (h == hipSuccess && res) h = launch_from_ncdhw(precision, res, (uint16_t *)(buf + ro), B, C, N, H, W, s);
-    int rc = h == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "bn_train: %s", hipGetErrorString(h));
-    if (rc == DFFW_OK)
-        rc = dffw_bn_train_forward(device, precision, buf + xo, B, C, N, H, W, gamma, beta, eps, momentum, running_mean, running_var, res ? buf + ro : nullptr,
-                                   relu, buf + yo, save_mean, save_invstd, buf + wo, wsb, hip_stream);
-    if (rc == DFFW_OK) {
-        h = launch_to_ncdhw(precision, (const uint16_t *)(buf + yo), y, B, C, N, H, W, s);
-        if (h != hipSuccess) rc = fail(DFFW_EHIP, "bn_train: %s", hipGetErrorString(h));
-    }
-    const hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(buf);
-    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
-    return rc;
-}
-
-int dffw_op_bn_train_backward(int device, int precision, const float *x, const float *y, const float *grad_y, int B, int C, int N, int H, int W,
-                              const float *gamma, const float *save_mean, const float *save_invstd, int relu, float *grad_x, float *grad_res,
-                              float *grad_gamma, float *grad_beta, void *hip_stream) {
-    dffw_set_last_op_kernels("");
-    int M;
-    if (int rc = check_shape(precision, B, C, N, H, W, &M)) return rc;
-    if (!x || !grad_y || !gamma || !save_mean || !save_invstd || !grad_gamma || !grad_beta) return fail(DFFW_EINVAL, "null argument");
-    if (relu && !y) return fail(DFFW_EINVAL, "the ReLU mask is read from y: y may be NULL only without ReLU");
-    if (grad_res && !grad_x) return fail(DFFW_EINVAL, "grad_res is written with grad_x");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    const int64_t rb = ((int64_t)M * prec_parts(precision) * C * 2 + 255) & ~(int64_t)255;
-    const int64_t wsb = workspace_bytes(M, C, Switches::read());
-    const int64_t xo = 0, yo = rb, go = 2 * rb, gxo = 3 * rb, gro = 4 * rb, wo = 5 * rb, total = wo + wsb;
-    char *buf = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, total));
-    hipError_t h = hipMemsetAsync(buf, 0xFF, total, s);
-    if (h == hipSuccess) h = launch_from_ncdhw(precision, x, (uint16_t *)(buf + xo), B, C, N, H, W, s);
-    if (h == hipSuccess && relu) h = launch_from_ncdhw(precision, y, (uint16_t *)(buf + yo), B, C, N, H, W, s);
-    if (h == hipSuccess) h = launch_from_ncdhw(precision, grad_y, (uint16_t *)(buf + go), B, C, N, H, W, s);
-    int rc = h == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "bn_train_backward: %s", hipGetErrorString(h));
-    if (rc == DFFW_OK)
-        rc = dffw_bn_train_backward(device, precision, buf + xo, relu ? buf + yo : nullptr, buf + go, B, C, N, H, W, gamma, save_mean, save_invstd, relu,
-                                    grad_x ? buf + gxo : nullptr, grad_res ? buf + gro : nullptr, grad_gamma, grad_beta, buf + wo, wsb, hip_stream);
-    if (rc == DFFW_OK && grad_x) {
-        h = launch_to_ncdhw(precision, (const uint16_t *)(buf + gxo), grad_x, B, C, N, H, W, s);
-        if (h == hipSuccess && grad_res) h = launch_to_ncdhw(precision, (const uint16_t *)(buf + gro), grad_res, B, C, N, H, W, s);
-        if (h != hipSuccess) rc = fail(DFFW_EHIP, "bn_train_backward: %s", hipGetErrorString(h));
-    }
-    const hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(buf);
-    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
-    return rc;
 }
 
 }  // extern "C"

@@ -39,4 +39,7 @@ hipError_t launch_bn_apply(int prec, int relu, int res, const BnArgs &a, int wgs
 hipError_t launch_bn_bwd_reduce(int prec, int relu, const BnArgs &a, int wgs, float *grad_gamma, float *grad_beta, hipStream_t s);
 hipError_t launch_bn_bwd_apply(int prec, int relu, int res, const BnArgs &a, int wgs, hipStream_t s);
 
+// dffw_bn.cpp: is (B, C, N, H, W) a volume train-mode BatchNorm serves?  DFFW_OK, or the error with its message set
+int bn_train_check(int precision, int B, int C, int N, int H, int W);
+
 }  // namespace dffw

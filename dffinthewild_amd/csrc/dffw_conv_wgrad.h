@@ -33,4 +33,8 @@ unsigned conv_wgrad_grid_x(const WgradArgs &a, int wgs);   // persistent grid of
 // conv_wgrad_kernel on the persistent grid, then conv_wgrad_finish: dw receives (Cg, Cf, kd, 3, 3) fp32
 hipError_t launch_conv_wgrad(int prec, int stride, const WgradArgs &a, unsigned grid_x, float *dw, hipStream_t s);
 
+// dffw_grad.cpp: is this one of the four geometries conv backward serves, on a shape it serves?  DFFW_OK, or the error with its message set
+int conv_backward_check(int precision, int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int stride[3], const int pad[3],
+                        int transposed);
+
 }  // namespace dffw

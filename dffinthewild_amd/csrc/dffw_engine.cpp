@@ -9,7 +9,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -201,6 +200,11 @@ static const Table &table_for(int net) {
     return net == DFFW_NET_E2E ? e2e : depth;
 }
 
+// the layers of one block as the table defines them (the single-operator entry points of dffw_ops.cpp pack them under the forward's names)
+std::vector<LayerDef> srd_layers(const std::string &p, int c) { Table t; t.srd(p, c); return t.layers; }
+std::vector<LayerDef> efd_layers(const std::string &p, int cin, int cout) { Table t; t.efd(p, cin, cout); return t.layers; }
+std::vector<LayerDef> of_block_layers(const std::string &p, int cin, int cout, int s) { Table t; t.of_block(p, cin, cout, s); return t.layers; }
+
 }  // namespace dffw
 
 using namespace dffw;
@@ -216,7 +220,7 @@ constexpr size_t SRD_TRACE_WORDS = 0;   // (the production srd kernels write no 
 // SRD block (DEN.py:317-330): x -> feat = relu(x + BN(conv(relu(BN(conv x))))) ; feat + relu(conv1(relu(conv3x1x1 feat)))
 // pooled (optional): receives max_pool(1,2,2) of the block's output when the fused attention kernel can produce it
 // on the way (else it is left empty and the caller pools separately).
-static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = nullptr) {
+Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled) {
     // the 8- / 16-channel block on whole 8 x 16 / 4 x 16 columns: one fused persistent kernel (dffw_srd_roll.hip)
     {
         auto c0 = r.e->convs.find(p + ".Focus_Measure.conv.0.0"), c2 = r.e->convs.find(p + ".Focus_Measure.conv.2.0");
@@ -303,7 +307,7 @@ static Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = 
 }
 
 // EFD block (DEN.py:306-315)
-static Act efd(Run &r, const std::string &p, const Act &x, Act *pooled = nullptr) {
+Act efd(Run &r, const std::string &p, const Act &x, Act *pooled) {
     auto ca = r.e->convs.find(p + ".stride_conv.0"), cb = r.e->convs.find(p + ".max_pooling.1.0");
     const int Ho = x.H / 2, Wo = x.W / 2;
     const double opx = (double)x.B * x.N * Ho * Wo;
@@ -895,300 +899,6 @@ int dffw_profile_collect(dffw_engine *e, dffw_prof_entry *out, int capacity) {
     return n;
 }
 
-// ---- single-operator entry points --------------------------------------------------------------
-int dffw_op_conv3d(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight,
-                   int Cout, const int kernel[3], const int stride[3], const int pad[3], const int dilation[3], int transposed,
-                   const float *bn, const float *conv_bias, const float *residual, int relu, float *y, void *hip_stream) {
-    return dffw_op_conv3d_ex(device, precision, x, B, Cin, N, H, W, weight, Cout, kernel, stride, pad, dilation, transposed, bn, conv_bias, residual, relu, y,
-                             nullptr, nullptr, nullptr, hip_stream);
-}
-
-int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight,
-                      int Cout, const int kernel[3], const int stride[3], const int pad[3], const int dilation[3], int transposed,
-                      const float *bn, const float *conv_bias, const float *residual, int relu, float *y, float *y_pre, const float *cls_weight,
-                      float *cls_score, void *hip_stream) {
-    if (!x || !weight || !y || !kernel || !stride || !pad || !dilation) return fail(DFFW_EINVAL, "null argument");
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (stride[0] != 1 || dilation[0] != 1) return fail(DFFW_EINVAL, "slice stride/dilation must be 1");
-    if (stride[1] != stride[2] || dilation[1] != dilation[2]) return fail(DFFW_EINVAL, "row/col stride and dilation must match");
-    if (Cout != 1 && Cout % 4) return fail(DFFW_EINVAL, "Cout must be 1 or a multiple of 4");
-    if (Cout > 128) return fail(DFFW_EINVAL, "Cout > 128 unsupported");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    LayerDef L{"op", "", Cin, Cout, kernel[0], kernel[1], kernel[2], stride[1], stride[2], pad[0], pad[1], pad[2],
-               dilation[1], dilation[2], transposed != 0, true, false};
-    if (transposed && !(kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && stride[1] == 2 && pad[0] == 1 && pad[1] == 1 && pad[2] == 1))
-        return fail(DFFW_EINVAL, "transposed conv supports only k3 s(1,2,2) p1 op(0,1,1)");
-    dffw_engine eng;
-    eng.device = device;
-    eng.prec = precision;
-    int rc = pack_conv(L, precision, weight, bn, conv_bias, eng.convs["op"]);
-    if (rc) return rc;
-    if ((cls_weight != nullptr) != (cls_score != nullptr)) return fail(DFFW_EINVAL, "cls_weight and cls_score go together");
-    if ((y_pre || cls_weight) && (Cout == 1 || Cout % 8)) return fail(DFFW_EINVAL, "second output / fused classifier need Cout %% 8 == 0");
-    if (cls_weight) {   // the 1x1x1 Cout -> 1 classifier applied to the final value (DEN.py:51-55), bias-free, no BatchNorm
-        LayerDef C{"cls", "", Cout, 1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 1, false, true, false};
-        rc = pack_conv(C, precision, cls_weight, nullptr, nullptr, eng.convs["cls"]);
-        if (rc) return rc;
-    }
-    const int parts = prec_parts(precision);
-    const int cpad = (Cin + 7) / 8 * 8;
-    const bool stem = (!transposed && kernel[0] == 1 && kernel[1] == 9 && kernel[2] == 9 && dilation[1] == 2 && pad[0] == 0 && pad[1] == 8 &&
-                       stride[1] == 1 && Cin == 3);
-    Act in;
-    in.B = B; in.N = N; in.H = H; in.W = stem ? W + 2 : W; in.C = cpad;
-    const int64_t in_bytes = in.pixels() * parts * cpad * 2;
-    HIPCHK(hipMalloc((void **)&in.p, in_bytes));
-    HIPCHK(hipMemsetAsync(in.p, 0, in_bytes, s));
-    if (stem) {
-        HIPCHK(launch_stack_in(precision, x, in.p, B, N, H, W, s));   // the stem's paired-pixel input format
-    } else if (cpad == Cin) {
-        HIPCHK(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, s));
-    } else {   // place the Cin real channels into the first channels of a zero-padded volume
-        float *xp = nullptr;
-        const int64_t plane = (int64_t)N * H * W;
-        HIPCHK(hipMalloc((void **)&xp, (size_t)B * cpad * plane * sizeof(float)));
-        HIPCHK(hipMemsetAsync(xp, 0, (size_t)B * cpad * plane * sizeof(float), s));
-        for (int b = 0; b < B; ++b)
-            HIPCHK(hipMemcpyAsync(xp + (int64_t)b * cpad * plane, x + (int64_t)b * Cin * plane, (size_t)Cin * plane * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
-        HIPCHK(launch_from_ncdhw(precision, xp, in.p, B, cpad, N, H, W, s));
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipFree(xp));
-    }
-    int Ho, Wo;
-    if (transposed) { Ho = 2 * H; Wo = 2 * W; }
-    else {
-        Ho = (H + 2 * pad[1] - dilation[1] * (kernel[1] - 1) - 1) / stride[1] + 1;
-        Wo = (W + 2 * pad[2] - dilation[2] * (kernel[2] - 1) - 1) / stride[2] + 1;
-    }
-    const int No = N + 2 * pad[0] - (kernel[0] - 1);
-    const int64_t opix = (int64_t)B * No * Ho * Wo;
-    // run through the same Run::conv path the graph uses, on a private workspace
-    const int64_t ws_bytes = 3 * (opix * parts * std::max(Cout, 4) * 2 + 4096) + 2 * (opix * 4 + 4096)
-                             + 8 * opix * ((Cout + 15) / 16 * 16) * 4 + 4096;   // + split-K partial sums (up to 8 splits)
-    char *ws = nullptr;
-    HIPCHK(hipMalloc((void **)&ws, ws_bytes));
-    // poisoned: 0xFF bytes are NaN in fp32, bf16 and fp16, so an output element no kernel stores, or a workspace value read before it is
-    // written, shows as NaN instead of as whatever the previous call left in a recycled block (the op path is test-only, not the forward's)
-    HIPCHK(hipMemsetAsync(ws, 0xFF, ws_bytes, s));
-    Run r(&eng, s, false, ws, ws_bytes);
-    Act res;
-    ConvOpt o;
-    o.relu = relu;
-    float *scoref = nullptr;
-    if (Cout == 1) {
-        scoref = (float *)r.raw(opix * sizeof(float));
-        o.outf = scoref;
-    } else if (residual) {
-        res = r.act(B, No, Ho, Wo, Cout);
-        HIPCHK(launch_from_ncdhw(precision, residual, res.p, B, Cout, No, Ho, Wo, s));
-        o.res0 = &res;
-    }
-    Act pre;
-    float *clsf = nullptr;
-    if (y_pre) o.out_pre = &pre;
-    if (cls_weight) {
-        clsf = (float *)r.raw(opix * sizeof(float));
-        o.cls = "cls";
-        o.cls_out = clsf;
-    }
-    Act out = r.conv("op", in, o);
-    rc = r.err;
-    if (rc == DFFW_OK) {
-        if (Cout == 1) rc = hipMemcpyAsync(y, scoref, opix * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "copy");
-        else rc = launch_to_ncdhw(precision, out.p, y, B, Cout, No, Ho, Wo, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "to_ncdhw");
-    }
-    if (rc == DFFW_OK && y_pre) rc = launch_to_ncdhw(precision, pre.p, y_pre, B, Cout, No, Ho, Wo, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "to_ncdhw");
-    if (rc == DFFW_OK && cls_weight)
-        rc = hipMemcpyAsync(cls_score, clsf, opix * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "copy");
-    hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(ws);
-    (void)hipFree(in.p);
-    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
-    return rc;
-}
-
-int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int B, int C, int N, int H, int W, float *y,
-                 void *hip_stream) {
-    if (!x || !y) return fail(DFFW_EINVAL, "null argument");
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (C % 8 || k < 1 || H % k || W % k) return fail(DFFW_EINVAL, "pool needs C %% 8 == 0 and H,W divisible by k");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    const int parts = prec_parts(precision);
-    uint16_t *a = nullptr, *b = nullptr;
-    const int64_t nin = (int64_t)B * N * H * W * parts * C, nout = (int64_t)B * N * (H / k) * (W / k) * parts * C;
-    HIPCHK(hipMalloc((void **)&a, nin * 2));
-    HIPCHK(hipMalloc((void **)&b, nout * 2));
-    HIPCHK(hipMemsetAsync(b, 0xFF, nout * 2, s));   // poisoned (NaN in every format): an output the pool kernel does not store shows
-    int rc = DFFW_OK;
-    hipError_t h = launch_from_ncdhw(precision, x, a, B, C, N, H, W, s);
-    if (h == hipSuccess) h = launch_pool(precision, mode, k, a, b, B, N, H, W, C, s);
-    if (h == hipSuccess) h = launch_to_ncdhw(precision, b, y, B, C, N, H / k, W / k, s);
-    if (h == hipSuccess) h = hipStreamSynchronize(s);
-    if (h != hipSuccess) rc = fail(DFFW_EHIP, "pool: %s", hipGetErrorString(h));
-    (void)hipFree(a);
-    (void)hipFree(b);
-    return rc;
-}
-
-// ---- block entry points (test-only): one SRD / EFD block of the front end through the graph's own srd() / efd() ----------------
-// The block's convs are packed under the keys the graph looks up (the forward's own layer names), so the shape-keyed branches of
-// pack_conv give the fused kernels the fragment sets they get in the forward, and the dispatch is srd() / efd() itself.
 const char *dffw_last_op_kernels(void) { return g_last_op_kernels.c_str(); }
-
-// Runs `body` twice on a private engine: a dry run sizes the workspace (as dffw_workspace_bytes does), the real run gets it filled with
-// 0xFF (NaN in every format, as in dffw_op_conv3d_ex).  Every launch of the real run is profiled; their kernel names, in launch order,
-// become dffw_last_op_kernels().
-static int run_block_op(dffw_engine &eng, hipStream_t s, const std::function<void(Run &)> &body) {
-    int64_t need;
-    {
-        Run d(&eng, s, true, nullptr, INT64_MAX / 2);
-        body(d);
-        if (!d.ok()) return d.err;
-        need = d.arena.peak();
-    }
-    const int64_t bytes = need + 65536;   // (the slack a caching allocator's block would give the forward's workspace)
-    char *ws = nullptr;
-    HIPCHK(hipMalloc((void **)&ws, bytes));
-    int rc = hipMemsetAsync(ws, 0xFF, bytes, s) == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "workspace memset");
-    if (rc == DFFW_OK) {
-        eng.profiling = true;
-        Run r(&eng, s, false, ws, bytes);
-        body(r);
-        rc = r.err;
-    }
-    const hipError_t se = hipStreamSynchronize(s);
-    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
-    for (const ProfRec &pr : eng.recs) g_last_op_kernels += (g_last_op_kernels.empty() ? "" : ";") + pr.kernel;
-    (void)hipFree(ws);
-    return rc;
-}
-
-int dffw_op_srd(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w0, const float *bn0,
-                const float *w2, const float *bn2, const float *w3, const float *w1, float *y, float *pooled, void *hip_stream) {
-    g_last_op_kernels.clear();
-    if (!x || !w0 || !bn0 || !w2 || !bn2 || !w3 || !w1 || !y) return fail(DFFW_EINVAL, "null argument");
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (C != 8 && C != 16 && C != 32) return fail(DFFW_EINVAL, "the SRD blocks have 8, 16 or 32 channels, got %d", C);
-    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
-    if (pooled && (H % 2 || W % 2)) return fail(DFFW_EINVAL, "the pooled copy needs even H and W, got %dx%d", H, W);
-    HIPCHK(hipSetDevice(device));
-    const std::string p = C == 8 ? "DFF_net.FM_measure.Focus_extraction.2" : C == 16 ? "DFF_net.FM_conv1.1" : "DFF_net.FM_conv2.1";
-    Table t;
-    t.srd(p, C);
-    dffw_engine eng;
-    eng.device = device;
-    eng.prec = precision;
-    const float *const wts[4] = {w0, w2, w3, w1}, *const bns[4] = {bn0, bn2, nullptr, nullptr};
-    for (int i = 0; i < 4; ++i) {
-        const int rc = pack_conv(t.layers[i], precision, wts[i], bns[i], nullptr, eng.convs[t.layers[i].conv]);
-        if (rc) return rc;
-    }
-    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
-        Act in = r.act(B, N, H, W, C);
-        if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, C, N, H, W, r.s), "from_ncdhw");
-        Act pl;
-        Act out = srd(r, p, in, true, pooled ? &pl : nullptr);
-        if (pooled && !pl.p) pl = r.pool(out, 0, 2);   // (this path writes no pooled copy: the engine's pool kernel, as efd() then runs it)
-        if (r.ok() && !r.dry) {
-            r.check(launch_to_ncdhw(precision, out.p, y, B, C, N, H, W, r.s), "to_ncdhw");
-            if (pooled) r.check(launch_to_ncdhw(precision, pl.p, pooled, B, C, N, H / 2, W / 2, r.s), "to_ncdhw");
-        }
-    });
-}
-
-int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *ws, const float *bns,
-                const float *wp, const float *bnp, int pooled_at_hand, float *y, void *hip_stream) {
-    g_last_op_kernels.clear();
-    if (!x || !ws || !bns || !wp || !bnp || !y) return fail(DFFW_EINVAL, "null argument");
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (Cin != 8 && Cin != 16) return fail(DFFW_EINVAL, "the EFD blocks have 8 or 16 input channels, got %d", Cin);
-    if (B < 1 || N < 1 || H < 2 || W < 2 || H % 2 || W % 2) return fail(DFFW_EINVAL, "bad shape (H and W must be even)");
-    HIPCHK(hipSetDevice(device));
-    const std::string p = Cin == 8 ? "DFF_net.FM_conv1.0" : "DFF_net.FM_conv2.0";
-    const int Cout = 2 * Cin;
-    Table t;
-    t.efd(p, Cin, Cout);
-    dffw_engine eng;
-    eng.device = device;
-    eng.prec = precision;
-    const float *const wts[2] = {ws, wp}, *const bnv[2] = {bns, bnp};
-    for (int i = 0; i < 2; ++i) {
-        const int rc = pack_conv(t.layers[i], precision, wts[i], bnv[i], nullptr, eng.convs[t.layers[i].conv]);
-        if (rc) return rc;
-    }
-    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
-        Act in = r.act(B, N, H, W, Cin);
-        if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, r.s), "from_ncdhw");
-        Act m;   // the pooled copy "at hand", as srd() leaves it for the forward's efd()
-        if (pooled_at_hand) m = r.pool(in, 0, 2);
-        Act out = efd(r, p, in, &m);
-        if (r.ok() && !r.dry) r.check(launch_to_ncdhw(precision, out.p, y, B, Cout, N, H / 2, W / 2, r.s), "to_ncdhw");
-    });
-}
-
-int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, int Cout, int stride,
-                     const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y, void *hip_stream) {
-    g_last_op_kernels.clear();
-    if (!x || !w0 || !bn0 || !w2 || !bn2 || !wf || !y) return fail(DFFW_EINVAL, "null argument");
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    static const struct { int cin, cout, s; const char *name; } blocks[] = {
-        {3, 8, 1, "OF_feature.0"}, {8, 8, 1, "OF_feature.1"}, {8, 16, 2, "OF_feature1.0"},
-        {16, 16, 1, "OF_feature1.1"}, {16, 32, 2, "OF_feature2.0"}, {32, 32, 1, "OF_feature2.1"}};
-    const char *name = nullptr;
-    for (const auto &b : blocks)
-        if (b.cin == Cin && b.cout == Cout && b.s == stride) name = b.name;
-    if (!name) return fail(DFFW_EINVAL, "no alignment feature block has (Cin, Cout, stride) = (%d, %d, %d)", Cin, Cout, stride);
-    if (B < 1 || N < 1 || H < 1 || W < 1 || H % stride || W % stride) return fail(DFFW_EINVAL, "bad shape (H and W must be multiples of the stride)");
-    HIPCHK(hipSetDevice(device));
-    const std::string p = std::string("optical_flow_aggregation.") + name;
-    Table t;
-    t.of_block(p, Cin, Cout, stride);
-    dffw_engine eng;
-    eng.device = device;
-    eng.prec = precision;
-    for (const LayerDef &L : t.layers) {   // as dffw_engine_create packs them: a stride-1 block's shortcut folded into conv.2
-        if (L.folded) continue;
-        const bool sc = !L.shortcut.empty();
-        const float *w = L.conv == p + ".conv.0.0" ? w0 : L.conv == p + ".conv.2.0" ? w2 : wf;
-        const float *bn = L.conv == p + ".conv.0.0" ? bn0 : L.conv == p + ".conv.2.0" ? bn2 : nullptr;
-        const int rc = pack_conv(L, precision, w, bn, nullptr, eng.convs[L.conv], sc ? wf : nullptr, sc ? Cin : 0);
-        if (rc) return rc;
-    }
-    return run_block_op(eng, (hipStream_t)hip_stream, [&](Run &r) {
-        Act out;
-        if (Cin == 3) {
-            out = of_first_block(r, p, x, B, N, H, W);
-        } else {
-            Act in = r.act(B, N, H, W, Cin);
-            if (r.ok() && !r.dry) r.check(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, r.s), "from_ncdhw");
-            out = of_block(r, p, in);
-        }
-        if (r.ok() && !r.dry) r.check(launch_to_ncdhw(precision, out.p, y, B, Cout, N, H / stride, W / stride, r.s), "to_ncdhw");
-    });
-}
-
-int dffw_op_regress(int device, const float *score, int B, int N, int h, int w, int H, int W, const float *focus_dists,
-                    const int64_t fd_strides[4], float *depth, void *hip_stream) {
-    if (!score || !focus_dists || !fd_strides || !depth) return fail(DFFW_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIPCHK(launch_regress(score, B, N, h, w, H, W, focus_dists, fd_strides[0], fd_strides[1], fd_strides[2], fd_strides[3], depth, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DFFW_OK;
-}
-
-int dffw_op_fov_warp(int device, const float *x, int B, int C, int N, int H, int W, const float *alpha, const float *fovs,
-                     int alpha_from_sample0, float *out, float *flow, void *hip_stream) {
-    if (!x || !alpha || !fovs || !out) return fail(DFFW_EINVAL, "null argument");
-    if (B < 1 || C < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIPCHK(launch_fov_warp(x, alpha, fovs, out, flow, B, C, N, H, W, alpha_from_sample0, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DFFW_OK;
-}
 
 }  // extern "C"

@@ -1,8 +1,6 @@
-// Backward of the aggregation network's plain convs: the C ABI of the weight-gradient kernels (dffw_conv_wgrad.hip) and the
-// single-operator entry point.  The data gradient is no kernel of its own: it is the adjoint conv, packed by pack_conv under a layer definition of
-// the adjoint geometry and run through the forward's own dispatch (dffw_op_conv3d -> Run::conv).
-#include <vector>
-
+// Backward of the aggregation network's plain convs: the C ABI of the weight-gradient kernels (dffw_conv_wgrad.hip).  The data
+// gradient is no kernel of its own: it is the adjoint conv, packed by pack_conv under a layer definition of the adjoint geometry and run through the
+// forward's own dispatch (dffw_op_conv3d_backward, dffw_ops.cpp: dffw_op_conv3d -> Run::conv).
 #include "dffw_conv_wgrad.h"
 #include "dffw_run.h"
 
@@ -77,6 +75,12 @@ WgradPlan plan_wgrad(Geometry g, const void *x, int B, int Cin, int N, int H, in
 
 }  // namespace
 
+int dffw::conv_backward_check(int precision, int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int stride[3], const int pad[3],
+                              int transposed) {
+    const Geometry g = geometry_of(kernel, stride, pad, transposed);
+    return g == G_NONE ? DFFW_EINVAL : check_shape(g, precision, B, Cin, N, H, W, Cout);
+}
+
 extern "C" {
 
 int64_t dffw_conv_wgrad_workspace_bytes(int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int stride[3], const int pad[3],
@@ -103,57 +107,6 @@ int dffw_conv_wgrad(int device, int precision, const void *x, int B, int Cin, in
     HIPCHK(launch_conv_wgrad(precision, p.stride, a, p.grid_x, grad_w, (hipStream_t)hip_stream));
     dffw_set_last_op_kernels((std::string(conv_wgrad_kernel_name(precision, p.stride)) + ";dffw::conv_wgrad_finish_kernel").c_str());
     return DFFW_OK;
-}
-
-int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight, int Cout,
-                            const int kernel[3], const int stride[3], const int pad[3], int transposed, const float *grad_y, float *grad_x,
-                            float *grad_w, void *hip_stream) {
-    dffw_set_last_op_kernels("");
-    const Geometry g = geometry_of(kernel, stride, pad, transposed);
-    if (g == G_NONE) return DFFW_EINVAL;
-    if (int rc = check_shape(g, precision, B, Cin, N, H, W, Cout)) return rc;
-    if (!x || !grad_y || (grad_x && !weight)) return fail(DFFW_EINVAL, "null argument");
-    // grad_y's shape follows from the geometry: the output volume of the forward
-    const int Ho = g == G_K333_T ? 2 * H : g == G_K333_S2 ? H / 2 : H, Wo = g == G_K333_T ? 2 * W : g == G_K333_S2 ? W / 2 : W;
-    const int one[3] = {1, 1, 1};
-    if (grad_x) {   // the adjoint conv over grad_y (Cout -> Cin channels), through dffw_op_conv3d: pack_conv + Run::conv, the forward's kernel choice
-        const int kd = kernel[0];
-        const int64_t taps = (int64_t)kd * 9;
-        int rc;
-        if (g == G_K333_S1 || g == G_K133_S1) {   // stride-1 conv of grad_y: filter flipped, in/out channels swapped, padding k - 1 - p (the same)
-            std::vector<float> wa((size_t)Cin * Cout * taps);
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci)
-                    for (int64_t t = 0; t < taps; ++t) wa[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = weight[((size_t)co * Cin + ci) * taps + t];
-            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, wa.data(), Cin, kernel, stride, pad, one, 0, nullptr, nullptr, nullptr, 0, grad_x,
-                                hip_stream);
-        } else {   // the stride-2 conv and the transposed conv are each other's adjoint, on the same filter
-            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, weight, Cin, kernel, stride, pad, one, g == G_K333_S2, nullptr, nullptr, nullptr, 0,
-                                grad_x, hip_stream);
-        }
-        if (rc) return rc;
-    }
-    if (!grad_w) return DFFW_OK;
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    const int parts = prec_parts(precision);
-    const int64_t xb = (int64_t)B * N * H * W * parts * Cin * 2, yb = (int64_t)B * N * Ho * Wo * parts * Cout * 2;
-    const int64_t wsb = dffw_conv_wgrad_workspace_bytes(B, Cin, N, H, W, Cout, kernel, stride, pad, transposed);
-    if (wsb <= 0) return fail(DFFW_EINVAL, "volume too large: the unit count does not fit 31 bits");
-    char *buf = nullptr;
-    const int64_t xo = 0, yo = (xb + 255) & ~(int64_t)255, wo = (yo + yb + 255) & ~(int64_t)255, total = wo + wsb;
-    HIPCHK(hipMalloc((void **)&buf, total));
-    // poisoned (NaN in every format): a record no kernel stores, or a partial read before it is written, shows
-    hipError_t h = hipMemsetAsync(buf, 0xFF, total, s);
-    if (h == hipSuccess) h = launch_from_ncdhw(precision, x, (uint16_t *)(buf + xo), B, Cin, N, H, W, s);
-    if (h == hipSuccess) h = launch_from_ncdhw(precision, grad_y, (uint16_t *)(buf + yo), B, Cout, N, Ho, Wo, s);
-    int rc = h == hipSuccess ? DFFW_OK : fail(DFFW_EHIP, "conv backward: %s", hipGetErrorString(h));
-    if (rc == DFFW_OK)
-        rc = dffw_conv_wgrad(device, precision, buf + xo, B, Cin, N, H, W, buf + yo, Cout, kernel, stride, pad, transposed, grad_w, buf + wo, wsb, hip_stream);
-    const hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(buf);
-    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
-    return rc;
 }
 
 }  // extern "C"

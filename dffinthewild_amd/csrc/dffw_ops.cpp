@@ -1,0 +1,382 @@
+// The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
+// bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
+// on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
+// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp) and stages the outputs back.
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "dffw_bn.h"
+#include "dffw_conv_wgrad.h"
+#include "dffw_run.h"
+
+using namespace dffw;
+
+namespace {
+
+// An op's private engine: the layers it packs, in the op's arithmetic.
+struct OpEngine : dffw_engine {
+    OpEngine(int device_, int prec_) { device = device_; prec = prec_; }
+};
+
+// The one device block of an op: synchronises the stream and frees on every way out of the scope, so no kernel outlives its workspace.
+struct OpBlock {
+    char *p = nullptr;
+    hipStream_t s;
+    explicit OpBlock(hipStream_t s_) : s(s_) {}
+    OpBlock(const OpBlock &) = delete;
+    OpBlock &operator=(const OpBlock &) = delete;
+    hipError_t alloc(int64_t bytes) { return hipMalloc((void **)&p, bytes); }
+    ~OpBlock() {
+        if (!p) return;
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(p);
+    }
+};
+
+// Runs `body` twice on `eng`: a dry run sizes the arena (as dffw_workspace_bytes does), the real run gets ONE private block of that size
+// filled with 0xFF -- NaN in fp32, bf16 and fp16, so an output element no kernel stores, or a workspace value read before it is written,
+// shows as NaN instead of as whatever a recycled block held.  Returns the first error, after the stream has drained.
+// record: every launch of the real run is profiled and the kernel names, in launch order, become dffw_last_op_kernels(); otherwise that
+// list is left to the body (the record-form ABIs set it themselves; the staging kernels are never part of it).
+int run_op(dffw_engine &eng, hipStream_t s, bool record, const std::function<void(Run &)> &body) {
+    int64_t need;
+    {
+        Run d(&eng, s, true, nullptr, INT64_MAX / 2);
+        body(d);
+        if (!d.ok()) return d.err;
+        need = d.arena.peak();
+    }
+    const int64_t bytes = need + 65536;   // (the slack a caching allocator's block would give the forward's workspace)
+    OpBlock ws(s);
+    HIPCHK(ws.alloc(bytes));
+    HIPCHK(hipMemsetAsync(ws.p, 0xFF, bytes, s));
+    eng.profiling = record;
+    int rc;
+    {
+        Run r(&eng, s, false, ws.p, bytes);
+        body(r);
+        rc = r.err;
+    }
+    const hipError_t se = hipStreamSynchronize(s);
+    if (rc == DFFW_OK && se != hipSuccess) rc = fail(DFFW_EHIP, "sync: %s", hipGetErrorString(se));
+    if (record) {
+        std::string names;
+        for (const ProfRec &pr : eng.recs) names += (names.empty() ? "" : ";") + pr.kernel;
+        dffw_set_last_op_kernels(names.c_str());
+    }
+    return rc;
+}
+
+// what a body does in the real run only
+bool real(const Run &r) { return r.ok() && !r.dry; }
+
+// an arena piece with the records of the fp32 NCDHW tensor x
+Act stage_in(Run &r, const float *x, int B, int C, int N, int H, int W) {
+    Act a = r.act(B, N, H, W, C);
+    if (real(r)) r.check(launch_from_ncdhw(r.e->prec, x, a.p, B, C, N, H, W, r.s), "from_ncdhw");
+    return a;
+}
+// ... and back: the records of `a` as the fp32 NCDHW tensor y
+void stage_out(Run &r, const Act &a, float *y) {
+    if (real(r)) r.check(launch_to_ncdhw(r.e->prec, a.p, y, a.B, a.C, a.N, a.H, a.W, r.s), "to_ncdhw");
+}
+// ... of an fp32 score volume of n values
+void copy_out(Run &r, const float *score, float *y, int64_t n) {
+    if (real(r)) r.check(hipMemcpyAsync(y, score, n * sizeof(float), hipMemcpyDeviceToDevice, r.s), "copy");
+}
+
+}  // namespace
+
+extern "C" {
+
+int dffw_op_conv3d(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight,
+                   int Cout, const int kernel[3], const int stride[3], const int pad[3], const int dilation[3], int transposed,
+                   const float *bn, const float *conv_bias, const float *residual, int relu, float *y, void *hip_stream) {
+    return dffw_op_conv3d_ex(device, precision, x, B, Cin, N, H, W, weight, Cout, kernel, stride, pad, dilation, transposed, bn, conv_bias, residual, relu, y,
+                             nullptr, nullptr, nullptr, hip_stream);
+}
+
+int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight,
+                      int Cout, const int kernel[3], const int stride[3], const int pad[3], const int dilation[3], int transposed,
+                      const float *bn, const float *conv_bias, const float *residual, int relu, float *y, float *y_pre, const float *cls_weight,
+                      float *cls_score, void *hip_stream) {
+    if (!x || !weight || !y || !kernel || !stride || !pad || !dilation) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (stride[0] != 1 || dilation[0] != 1) return fail(DFFW_EINVAL, "slice stride/dilation must be 1");
+    if (stride[1] != stride[2] || dilation[1] != dilation[2]) return fail(DFFW_EINVAL, "row/col stride and dilation must match");
+    if (Cout != 1 && Cout % 4) return fail(DFFW_EINVAL, "Cout must be 1 or a multiple of 4");
+    if (Cout > 128) return fail(DFFW_EINVAL, "Cout > 128 unsupported");
+    HIPCHK(hipSetDevice(device));
+    LayerDef L{"op", "", Cin, Cout, kernel[0], kernel[1], kernel[2], stride[1], stride[2], pad[0], pad[1], pad[2],
+               dilation[1], dilation[2], transposed != 0, true, false};
+    if (transposed && !(kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && stride[1] == 2 && pad[0] == 1 && pad[1] == 1 && pad[2] == 1))
+        return fail(DFFW_EINVAL, "transposed conv supports only k3 s(1,2,2) p1 op(0,1,1)");
+    OpEngine eng(device, precision);
+    int rc = pack_conv(L, precision, weight, bn, conv_bias, eng.convs["op"]);
+    if (rc) return rc;
+    if ((cls_weight != nullptr) != (cls_score != nullptr)) return fail(DFFW_EINVAL, "cls_weight and cls_score go together");
+    if ((y_pre || cls_weight) && (Cout == 1 || Cout % 8)) return fail(DFFW_EINVAL, "second output / fused classifier need Cout %% 8 == 0");
+    if (cls_weight) {   // the 1x1x1 Cout -> 1 classifier applied to the final value (DEN.py:51-55), bias-free, no BatchNorm
+        LayerDef C{"cls", "", Cout, 1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 1, false, true, false};
+        rc = pack_conv(C, precision, cls_weight, nullptr, nullptr, eng.convs["cls"]);
+        if (rc) return rc;
+    }
+    const int cpad = (Cin + 7) / 8 * 8;
+    const bool stem = (!transposed && kernel[0] == 1 && kernel[1] == 9 && kernel[2] == 9 && dilation[1] == 2 && pad[0] == 0 && pad[1] == 8 &&
+                       stride[1] == 1 && Cin == 3);
+    // through the same Run::conv path the graph uses; dffw_last_op_kernels() is not this op's to set
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        // the input records; zero-filled first (the arena is 0xFF) where the volume is wider than the tensor: the stem's paired-pixel volume of
+        // width W + 2 and the volume whose channels are padded to a multiple of 8
+        Act in = r.act(B, N, H, stem ? W + 2 : W, cpad);
+        const int64_t plane = (int64_t)N * H * W;
+        float *xp = !stem && cpad != Cin ? (float *)r.raw(B * cpad * plane * (int64_t)sizeof(float)) : nullptr;
+        if (real(r)) {
+            if (stem || xp) r.check(hipMemsetAsync(in.p, 0, (size_t)in.pixels() * prec_parts(precision) * cpad * 2, r.s), "input memset");
+            if (stem) {
+                r.check(launch_stack_in(precision, x, in.p, B, N, H, W, r.s), "stack_in");   // the stem's paired-pixel input format
+            } else if (!xp) {
+                r.check(launch_from_ncdhw(precision, x, in.p, B, Cin, N, H, W, r.s), "from_ncdhw");
+            } else {   // the Cin real channels in the first channels of a zero-padded fp32 volume
+                r.check(hipMemsetAsync(xp, 0, (size_t)B * cpad * plane * sizeof(float), r.s), "input memset");
+                for (int b = 0; b < B && r.ok(); ++b)
+                    r.check(hipMemcpyAsync(xp + (int64_t)b * cpad * plane, x + (int64_t)b * Cin * plane, (size_t)Cin * plane * sizeof(float),
+                                           hipMemcpyDeviceToDevice, r.s), "copy");
+                if (r.ok()) r.check(launch_from_ncdhw(precision, xp, in.p, B, cpad, N, H, W, r.s), "from_ncdhw");
+            }
+        }
+        const int No = N + 2 * pad[0] - (kernel[0] - 1);
+        const int Ho = transposed ? 2 * H : (H + 2 * pad[1] - dilation[1] * (kernel[1] - 1) - 1) / stride[1] + 1;
+        const int Wo = transposed ? 2 * W : (W + 2 * pad[2] - dilation[2] * (kernel[2] - 1) - 1) / stride[2] + 1;
+        const int64_t opix = (int64_t)B * No * Ho * Wo;
+        ConvOpt o;
+        o.relu = relu;
+        Act res, pre;
+        if (Cout == 1) {
+            o.outf = (float *)r.raw(opix * sizeof(float));
+        } else if (residual) {
+            res = stage_in(r, residual, B, Cout, No, Ho, Wo);
+            o.res0 = &res;
+        }
+        if (y_pre) o.out_pre = &pre;
+        if (cls_weight) {
+            o.cls = "cls";
+            o.cls_out = (float *)r.raw(opix * sizeof(float));
+        }
+        Act out = r.conv("op", in, o);
+        if (Cout == 1) copy_out(r, o.outf, y, opix);
+        else stage_out(r, out, y);
+        if (y_pre) stage_out(r, pre, y_pre);
+        if (cls_weight) copy_out(r, o.cls_out, cls_score, opix);
+    });
+}
+
+int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int B, int C, int N, int H, int W, float *y,
+                 void *hip_stream) {
+    if (!x || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (C % 8 || k < 1 || H % k || W % k) return fail(DFFW_EINVAL, "pool needs C %% 8 == 0 and H,W divisible by k");
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act in = stage_in(r, x, B, C, N, H, W);
+        stage_out(r, r.pool(in, mode, k), y);
+    });
+}
+
+// ---- block entry points: one SRD / EFD block of the front end, one feature block of the alignment network, through the graph's own
+// srd() / efd() / of_block().  The block's convs are packed under the keys the graph looks up, so the dispatch is the forward's itself.
+int dffw_op_srd(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w0, const float *bn0,
+                const float *w2, const float *bn2, const float *w3, const float *w1, float *y, float *pooled, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!x || !w0 || !bn0 || !w2 || !bn2 || !w3 || !w1 || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (C != 8 && C != 16 && C != 32) return fail(DFFW_EINVAL, "the SRD blocks have 8, 16 or 32 channels, got %d", C);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
+    if (pooled && (H % 2 || W % 2)) return fail(DFFW_EINVAL, "the pooled copy needs even H and W, got %dx%d", H, W);
+    HIPCHK(hipSetDevice(device));
+    const std::string p = C == 8 ? "DFF_net.FM_measure.Focus_extraction.2" : C == 16 ? "DFF_net.FM_conv1.1" : "DFF_net.FM_conv2.1";
+    const std::vector<LayerDef> layers = srd_layers(p, C);
+    const float *const wts[4] = {w0, w2, w3, w1}, *const bns[4] = {bn0, bn2, nullptr, nullptr};
+    OpEngine eng(device, precision);
+    for (int i = 0; i < 4; ++i) {
+        const int rc = pack_conv(layers[i], precision, wts[i], bns[i], nullptr, eng.convs[layers[i].conv]);
+        if (rc) return rc;
+    }
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act in = stage_in(r, x, B, C, N, H, W);
+        Act pl;
+        Act out = srd(r, p, in, true, pooled ? &pl : nullptr);
+        if (pooled && !pl.p) pl = r.pool(out, 0, 2);   // (this path writes no pooled copy: the engine's pool kernel, as efd() then runs it)
+        stage_out(r, out, y);
+        if (pooled) stage_out(r, pl, pooled);
+    });
+}
+
+int dffw_op_efd(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *ws, const float *bns,
+                const float *wp, const float *bnp, int pooled_at_hand, float *y, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!x || !ws || !bns || !wp || !bnp || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (Cin != 8 && Cin != 16) return fail(DFFW_EINVAL, "the EFD blocks have 8 or 16 input channels, got %d", Cin);
+    if (B < 1 || N < 1 || H < 2 || W < 2 || H % 2 || W % 2) return fail(DFFW_EINVAL, "bad shape (H and W must be even)");
+    HIPCHK(hipSetDevice(device));
+    const std::string p = Cin == 8 ? "DFF_net.FM_conv1.0" : "DFF_net.FM_conv2.0";
+    const std::vector<LayerDef> layers = efd_layers(p, Cin, 2 * Cin);
+    const float *const wts[2] = {ws, wp}, *const bnv[2] = {bns, bnp};
+    OpEngine eng(device, precision);
+    for (int i = 0; i < 2; ++i) {
+        const int rc = pack_conv(layers[i], precision, wts[i], bnv[i], nullptr, eng.convs[layers[i].conv]);
+        if (rc) return rc;
+    }
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act in = stage_in(r, x, B, Cin, N, H, W);
+        Act m;   // the pooled copy "at hand", as srd() leaves it for the forward's efd()
+        if (pooled_at_hand) m = r.pool(in, 0, 2);
+        stage_out(r, efd(r, p, in, &m), y);
+    });
+}
+
+int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, int Cout, int stride,
+                     const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!x || !w0 || !bn0 || !w2 || !bn2 || !wf || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    static const struct { int cin, cout, s; const char *name; } blocks[] = {
+        {3, 8, 1, "OF_feature.0"}, {8, 8, 1, "OF_feature.1"}, {8, 16, 2, "OF_feature1.0"},
+        {16, 16, 1, "OF_feature1.1"}, {16, 32, 2, "OF_feature2.0"}, {32, 32, 1, "OF_feature2.1"}};
+    const char *name = nullptr;
+    for (const auto &b : blocks)
+        if (b.cin == Cin && b.cout == Cout && b.s == stride) name = b.name;
+    if (!name) return fail(DFFW_EINVAL, "no alignment feature block has (Cin, Cout, stride) = (%d, %d, %d)", Cin, Cout, stride);
+    if (B < 1 || N < 1 || H < 1 || W < 1 || H % stride || W % stride) return fail(DFFW_EINVAL, "bad shape (H and W must be multiples of the stride)");
+    HIPCHK(hipSetDevice(device));
+    const std::string p = std::string("optical_flow_aggregation.") + name;
+    OpEngine eng(device, precision);
+    for (const LayerDef &L : of_block_layers(p, Cin, Cout, stride)) {   // as dffw_engine_create packs them: a stride-1 block's shortcut folded into conv.2
+        if (L.folded) continue;
+        const bool sc = !L.shortcut.empty();
+        const float *w = L.conv == p + ".conv.0.0" ? w0 : L.conv == p + ".conv.2.0" ? w2 : wf;
+        const float *bn = L.conv == p + ".conv.0.0" ? bn0 : L.conv == p + ".conv.2.0" ? bn2 : nullptr;
+        const int rc = pack_conv(L, precision, w, bn, nullptr, eng.convs[L.conv], sc ? wf : nullptr, sc ? Cin : 0);
+        if (rc) return rc;
+    }
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act out;
+        if (Cin == 3) {
+            out = of_first_block(r, p, x, B, N, H, W);
+        } else {
+            Act in = stage_in(r, x, B, Cin, N, H, W);
+            out = of_block(r, p, in);
+        }
+        stage_out(r, out, y);
+    });
+}
+
+int dffw_op_regress(int device, const float *score, int B, int N, int h, int w, int H, int W, const float *focus_dists,
+                    const int64_t fd_strides[4], float *depth, void *hip_stream) {
+    if (!score || !focus_dists || !fd_strides || !depth) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIPCHK(launch_regress(score, B, N, h, w, H, W, focus_dists, fd_strides[0], fd_strides[1], fd_strides[2], fd_strides[3], depth, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DFFW_OK;
+}
+
+int dffw_op_fov_warp(int device, const float *x, int B, int C, int N, int H, int W, const float *alpha, const float *fovs,
+                     int alpha_from_sample0, float *out, float *flow, void *hip_stream) {
+    if (!x || !alpha || !fovs || !out) return fail(DFFW_EINVAL, "null argument");
+    if (B < 1 || C < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIPCHK(launch_fov_warp(x, alpha, fovs, out, flow, B, C, N, H, W, alpha_from_sample0, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DFFW_OK;
+}
+
+// ---- training ops: the record-form ABIs (dffw_conv_wgrad, dffw_bn_train_*) between a stage-in and a stage-out.  Those calls set
+// dffw_last_op_kernels() themselves; their bodies need an engine only for its precision.
+int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight, int Cout,
+                            const int kernel[3], const int stride[3], const int pad[3], int transposed, const float *grad_y, float *grad_x,
+                            float *grad_w, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = conv_backward_check(precision, B, Cin, N, H, W, Cout, kernel, stride, pad, transposed)) return rc;
+    if (!x || !grad_y || (grad_x && !weight)) return fail(DFFW_EINVAL, "null argument");
+    // grad_y's shape follows from the geometry: the output volume of the forward
+    const bool s2 = stride[1] == 2 && !transposed;
+    const int Ho = transposed ? 2 * H : s2 ? H / 2 : H, Wo = transposed ? 2 * W : s2 ? W / 2 : W;
+    const int one[3] = {1, 1, 1};
+    if (grad_x) {   // the adjoint conv over grad_y (Cout -> Cin channels), through dffw_op_conv3d: pack_conv + Run::conv, the forward's kernel choice
+        const int64_t taps = (int64_t)kernel[0] * 9;
+        int rc;
+        if (!transposed && !s2) {   // stride-1 conv of grad_y: filter flipped, in/out channels swapped, padding k - 1 - p (the same)
+            std::vector<float> wa((size_t)Cin * Cout * taps);
+            for (int co = 0; co < Cout; ++co)
+                for (int ci = 0; ci < Cin; ++ci)
+                    for (int64_t t = 0; t < taps; ++t) wa[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = weight[((size_t)co * Cin + ci) * taps + t];
+            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, wa.data(), Cin, kernel, stride, pad, one, 0, nullptr, nullptr, nullptr, 0, grad_x,
+                                hip_stream);
+        } else {   // the stride-2 conv and the transposed conv are each other's adjoint, on the same filter
+            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, weight, Cin, kernel, stride, pad, one, s2, nullptr, nullptr, nullptr, 0,
+                                grad_x, hip_stream);
+        }
+        if (rc) return rc;
+    }
+    if (!grad_w) return DFFW_OK;
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = dffw_conv_wgrad_workspace_bytes(B, Cin, N, H, W, Cout, kernel, stride, pad, transposed);
+    if (wsb <= 0) return fail(DFFW_EINVAL, "volume too large: the unit count does not fit 31 bits");
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act xa = stage_in(r, x, B, Cin, N, H, W), ya = stage_in(r, grad_y, B, Cout, N, Ho, Wo);
+        void *ws = r.raw(wsb);
+        if (real(r)) r.err = dffw_conv_wgrad(device, precision, xa.p, B, Cin, N, H, W, ya.p, Cout, kernel, stride, pad, transposed, grad_w, ws, wsb, r.s);
+    });
+}
+
+int dffw_op_bn_train(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *gamma, const float *beta, double eps,
+                     double momentum, float *running_mean, float *running_var, const float *res, int relu, float *y, float *save_mean,
+                     float *save_invstd, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = bn_train_check(precision, B, C, N, H, W)) return rc;
+    if (!(eps > 0.0)) return fail(DFFW_EINVAL, "eps must be positive, got %g", eps);
+    if (!x || !gamma || !beta || !y || !save_mean || !save_invstd) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = dffw_bn_train_workspace_bytes(B, C, N, H, W);
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act xa = stage_in(r, x, B, C, N, H, W), ra = res ? stage_in(r, res, B, C, N, H, W) : Act();
+        Act ya = r.act(B, N, H, W, C);
+        void *ws = r.raw(wsb);
+        if (real(r))
+            r.err = dffw_bn_train_forward(device, precision, xa.p, B, C, N, H, W, gamma, beta, eps, momentum, running_mean, running_var, ra.p, relu, ya.p,
+                                          save_mean, save_invstd, ws, wsb, r.s);
+        stage_out(r, ya, y);
+    });
+}
+
+int dffw_op_bn_train_backward(int device, int precision, const float *x, const float *y, const float *grad_y, int B, int C, int N, int H, int W,
+                              const float *gamma, const float *save_mean, const float *save_invstd, int relu, float *grad_x, float *grad_res,
+                              float *grad_gamma, float *grad_beta, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = bn_train_check(precision, B, C, N, H, W)) return rc;
+    if (!x || !grad_y || !gamma || !save_mean || !save_invstd || !grad_gamma || !grad_beta) return fail(DFFW_EINVAL, "null argument");
+    if (relu && !y) return fail(DFFW_EINVAL, "the ReLU mask is read from y: y may be NULL only without ReLU");
+    if (grad_res && !grad_x) return fail(DFFW_EINVAL, "grad_res is written with grad_x");
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = dffw_bn_train_workspace_bytes(B, C, N, H, W);
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act xa = stage_in(r, x, B, C, N, H, W), ya = relu ? stage_in(r, y, B, C, N, H, W) : Act(), ga = stage_in(r, grad_y, B, C, N, H, W);
+        Act gx = grad_x ? r.act(B, N, H, W, C) : Act(), gr = grad_res ? r.act(B, N, H, W, C) : Act();
+        void *ws = r.raw(wsb);
+        if (real(r))
+            r.err = dffw_bn_train_backward(device, precision, xa.p, ya.p, ga.p, B, C, N, H, W, gamma, save_mean, save_invstd, relu, gx.p, gr.p, grad_gamma,
+                                           grad_beta, ws, wsb, r.s);
+        if (grad_x) stage_out(r, gx, grad_x);
+        if (grad_res) stage_out(r, gr, grad_res);
+    });
+}
+
+}  // extern "C"

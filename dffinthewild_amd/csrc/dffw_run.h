@@ -1,6 +1,6 @@
 // Private to the host side of libdffw.so: the workspace arena, the engine object, the DFFW_* switch snapshot and the per-forward
-// executor state (Run) that the graphs of dffw_engine.cpp (depth network, C ABI) and dffw_align.cpp (alignment network) and the conv
-// dispatch of dffw_dispatch.cpp share.  No kernel includes this.
+// executor state (Run) that the graphs of dffw_engine.cpp (depth network, C ABI) and dffw_align.cpp (alignment network), the conv
+// dispatch of dffw_dispatch.cpp and the single-operator entry points of dffw_ops.cpp share.  No kernel includes this.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -563,5 +563,13 @@ int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], in
 int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W, float *const out[4], float *aligned);
 Act of_block(Run &r, const std::string &p, const Act &x);
 Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W);
+// the front end's blocks (dffw_engine.cpp).  srd: pooled (optional) receives max_pool(1,2,2) of the output when the fused kernel writes it on the way;
+// efd: pooled (optional) is that copy of x, at hand
+Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = nullptr);
+Act efd(Run &r, const std::string &p, const Act &x, Act *pooled = nullptr);
+// the layers of one block under prefix p, as the layer table of dffw_engine.cpp defines them
+std::vector<LayerDef> srd_layers(const std::string &p, int c);
+std::vector<LayerDef> efd_layers(const std::string &p, int cin, int cout);
+std::vector<LayerDef> of_block_layers(const std::string &p, int cin, int cout, int s);
 
 }  // namespace dffw

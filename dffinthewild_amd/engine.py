@@ -186,6 +186,16 @@ def _f32(t):
     return ctypes.cast(t.data_ptr(), POINTER(c_float))
 
 
+def _dev(t):
+    """Index of the GPU that holds the tensor ``t``."""
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
+def _ptr(t):
+    """``t``'s device address as a C pointer argument; NULL for None."""
+    return c_void_p(t.data_ptr()) if t is not None else None
+
+
 class Engine:
     """Owns one ``dffw_engine`` (packed weights on one GPU).  Thread-compatible: calls on engines
     of different devices may run concurrently (ctypes releases the GIL)."""
@@ -286,14 +296,13 @@ class Engine:
         optrs = (c_void_p * 4)(*[o.data_ptr() for o in outs])
         with self._lock, torch.cuda.device(self.index):
             def args(ws):
-                return [self._h, c_void_p(FS.data_ptr()), c_void_p(fd.data_ptr()), strides, B, N, H, W, optrs,
-                        c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(self.index)]
+                return [self._h, _ptr(FS), _ptr(fd), strides, B, N, H, W, optrs, _ptr(ws), ws.numel(), _stream_ptr(self.index)]
             if not taps:
                 _check(self._call_ws(B, N, H, W, 0, lambda ws: lib.dffw_forward(*args(ws))), "dffw_forward")
                 return tuple(outs)
             shapes = _tap_shapes(B, N, H, W)
             bufs = {nm: torch.empty(shapes[nm], dtype=torch.float32, device=FS.device) for nm in taps}
-            tarr = (_Tap * len(bufs))(*[_Tap(nm.encode(), c_void_p(t.data_ptr()), t.numel()) for nm, t in bufs.items()])
+            tarr = (_Tap * len(bufs))(*[_Tap(nm.encode(), _ptr(t), t.numel()) for nm, t in bufs.items()])
             _check(self._call_ws(B, N, H, W, 0, lambda ws: lib.dffw_forward_taps(*args(ws), tarr, len(bufs))), "dffw_forward_taps")
             return tuple(outs), bufs
 
@@ -309,8 +318,8 @@ class Engine:
         with self._lock, torch.cuda.device(self.index):
             st5 = (c_int64 * 5)(*strides)
             _check(self._call_ws(B, N, H, W, B * 3 * N * H * W * 4 + 256,
-                                 lambda ws: lib.dffw_forward_raw(self._h, c_void_p(raw), dtype, st5, h, w, c_void_p(fd.data_ptr()), fst,
-                                                                 B, N, H, W, optrs, c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(self.index))),
+                                 lambda ws: lib.dffw_forward_raw(self._h, c_void_p(raw), dtype, st5, h, w, _ptr(fd), fst,
+                                                                 B, N, H, W, optrs, _ptr(ws), ws.numel(), _stream_ptr(self.index))),
                    "dffw_forward_raw")
         return tuple(outs)
 
@@ -331,12 +340,11 @@ class Engine:
             if taps:
                 shapes = _tap_shapes(B, N, H, W)
                 bufs = {nm: torch.empty(shapes[nm], dtype=torch.float32, device=FS.device) for nm in taps}
-                tarr = (_Tap * len(bufs))(*[_Tap(nm.encode(), c_void_p(t.data_ptr()), t.numel()) for nm, t in bufs.items()])
+                tarr = (_Tap * len(bufs))(*[_Tap(nm.encode(), _ptr(t), t.numel()) for nm, t in bufs.items()])
                 nt = len(bufs)
             _check(self._call_ws(B, N, H, W, 0,
-                                 lambda ws: lib.dffw_forward_e2e(self._h, c_void_p(FS.data_ptr()), c_void_p(fd.data_ptr()), strides,
-                                                                 c_void_p(fov.data_ptr()), B, N, H, W, optrs, c_void_p(aligned.data_ptr()),
-                                                                 c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(self.index), tarr, nt)),
+                                 lambda ws: lib.dffw_forward_e2e(self._h, _ptr(FS), _ptr(fd), strides, _ptr(fov), B, N, H, W, optrs, _ptr(aligned),
+                                                                 _ptr(ws), ws.numel(), _stream_ptr(self.index), tarr, nt)),
                    "dffw_forward_e2e")
         res = tuple(outs) + (aligned,)
         return (res, bufs) if taps else res
@@ -385,19 +393,17 @@ def op_conv3d(x, weight, *, stride=1, pad=0, dilation=1, transposed=False, bn=No
     y = torch.empty((B, No, Ho, Wo) if Cout == 1 else (B, Cout, No, Ho, Wo), dtype=torch.float32, device=x.device)
     x = x.contiguous()
     res = residual.contiguous() if residual is not None else None
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     ex = want_pre or cls_weight is not None
     y_pre = torch.empty_like(y) if want_pre else None
     cw = cls_weight.detach().to("cpu", torch.float32).reshape(-1).contiguous() if cls_weight is not None else None
     score = torch.empty((B, No, Ho, Wo), dtype=torch.float32, device=x.device) if cw is not None else None
     with torch.cuda.device(dev):
-        args = (dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, Cin, N, H, W, _f32(w), Cout,
+        args = (dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _f32(w), Cout,
                 (c_int * 3)(*k), s, p, d, int(transposed),
-                _f32(bnh) if bnh is not None else None, _f32(bh) if bh is not None else None,
-                c_void_p(res.data_ptr()) if res is not None else None, relu, c_void_p(y.data_ptr()))
+                _f32(bnh) if bnh is not None else None, _f32(bh) if bh is not None else None, _ptr(res), relu, _ptr(y))
         if ex:
-            _check(lib.dffw_op_conv3d_ex(*args, c_void_p(y_pre.data_ptr()) if want_pre else None, _f32(cw) if cw is not None else None,
-                                         c_void_p(score.data_ptr()) if cw is not None else None, _stream_ptr(dev)), "dffw_op_conv3d_ex")
+            _check(lib.dffw_op_conv3d_ex(*args, _ptr(y_pre), _f32(cw) if cw is not None else None, _ptr(score), _stream_ptr(dev)), "dffw_op_conv3d_ex")
             return y, y_pre, score
         _check(lib.dffw_op_conv3d(*args, _stream_ptr(dev)), "dffw_op_conv3d")
     return y
@@ -431,14 +437,13 @@ def op_conv3d_backward(x, weight, grad_y, *, stride=1, pad=0, dilation=1, transp
     s, p = _i3(stride), _i3(pad)
     w = weight.detach().to("cpu", torch.float32).contiguous()
     x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     gx = torch.empty_like(x) if "x" in need else None
     gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
 
     def call(with_x, with_w):
-        return lib.dffw_op_conv3d_backward(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), s, p,
-                                           int(transposed), c_void_p(grad_y.data_ptr()), c_void_p(gx.data_ptr()) if with_x else None,
-                                           c_void_p(gw.data_ptr()) if with_w else None, _stream_ptr(dev))
+        return lib.dffw_op_conv3d_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), s, p,
+                                           int(transposed), _ptr(grad_y), _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
     with torch.cuda.device(dev):
         # the C entry point takes grad_y's shape from the geometry: its own refusals first (a call with no output launches nothing), then the tensor
         _check(call(False, False), "dffw_op_conv3d_backward")
@@ -478,14 +483,13 @@ def op_bn_train(x, gamma, beta, running_mean=None, running_var=None, *, residual
     x = x.detach().float().contiguous()
     res = residual.detach().float().contiguous() if residual is not None else None
     g, b = _bn_vec(gamma, C, x.device, "gamma"), _bn_vec(beta, C, x.device, "beta")
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     y = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty_like(mean)
-    ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_bn_train(dev, PRECISIONS[precision], ptr(x), B, C, N, H, W, ptr(g), ptr(b), float(eps), float(momentum), ptr(running_mean),
-                                    ptr(running_var), ptr(res), int(bool(relu)), ptr(y), ptr(mean), ptr(invstd), _stream_ptr(dev)), "dffw_op_bn_train")
+        _check(lib.dffw_op_bn_train(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, _ptr(g), _ptr(b), float(eps), float(momentum), _ptr(running_mean),
+                                    _ptr(running_var), _ptr(res), int(bool(relu)), _ptr(y), _ptr(mean), _ptr(invstd), _stream_ptr(dev)), "dffw_op_bn_train")
     return y, mean, invstd
 
 
@@ -504,15 +508,14 @@ def op_bn_train_backward(x, y, grad_y, gamma, save_mean, save_invstd, *, relu=Fa
     x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
     y = y.detach().float().contiguous() if relu else None
     g, mean, invstd = (_bn_vec(t, C, x.device, n) for t, n in ((gamma, "gamma"), (save_mean, "save_mean"), (save_invstd, "save_invstd")))
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     gx = torch.empty_like(x) if "x" in need else None
     gres = torch.empty_like(x) if residual and gx is not None else None
     gg = torch.empty(C, dtype=torch.float32, device=x.device)
     gb = torch.empty_like(gg)
-    ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_bn_train_backward(dev, PRECISIONS[precision], ptr(x), ptr(y), ptr(grad_y), B, C, N, H, W, ptr(g), ptr(mean), ptr(invstd),
-                                             int(bool(relu)), ptr(gx), ptr(gres), ptr(gg), ptr(gb), _stream_ptr(dev)), "dffw_op_bn_train_backward")
+        _check(lib.dffw_op_bn_train_backward(dev, PRECISIONS[precision], _ptr(x), _ptr(y), _ptr(grad_y), B, C, N, H, W, _ptr(g), _ptr(mean), _ptr(invstd),
+                                             int(bool(relu)), _ptr(gx), _ptr(gres), _ptr(gg), _ptr(gb), _stream_ptr(dev)), "dffw_op_bn_train_backward")
     return gx, gres, gg, gb
 
 
@@ -546,10 +549,9 @@ def op_srd(x, w0, bn0, w2, bn2, w3, w1, *, pooled=False, precision="bf16x3"):
     y = torch.empty_like(x)
     pl = torch.empty((B, C, N, H // 2, W // 2), dtype=torch.float32, device=x.device) if pooled else None
     host = [_host_f32(w0), _bn_host(bn0), _host_f32(w2), _bn_host(bn2), _host_f32(w3), _host_f32(w1)]
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_srd(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, *[_f32(t) for t in host],
-                               c_void_p(y.data_ptr()), c_void_p(pl.data_ptr()) if pooled else None, _stream_ptr(dev)), "dffw_op_srd")
+        _check(lib.dffw_op_srd(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, *[_f32(t) for t in host], _ptr(y), _ptr(pl), _stream_ptr(dev)), "dffw_op_srd")
     return (y, pl) if pooled else y
 
 
@@ -560,10 +562,10 @@ def op_efd(x, ws, bns, wp, bnp, *, pooled_at_hand=True, precision="bf16x3"):
     x = x.contiguous()
     y = torch.empty((B, 2 * C, N, H // 2, W // 2), dtype=torch.float32, device=x.device)
     host = [_host_f32(ws), _bn_host(bns), _host_f32(wp), _bn_host(bnp)]
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_efd(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, *[_f32(t) for t in host],
-                               int(bool(pooled_at_hand)), c_void_p(y.data_ptr()), _stream_ptr(dev)), "dffw_op_efd")
+        _check(lib.dffw_op_efd(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, *[_f32(t) for t in host],
+                               int(bool(pooled_at_hand)), _ptr(y), _stream_ptr(dev)), "dffw_op_efd")
     return y
 
 
@@ -576,10 +578,10 @@ def op_of_block(x, w0, bn0, w2, bn2, wf, *, stride=1, precision="bf16x3"):
     x = x.contiguous()
     y = torch.empty((B, Cout, N, H // stride, W // stride), dtype=torch.float32, device=x.device)
     host = [_host_f32(w0), _bn_host(bn0), _host_f32(w2), _bn_host(bn2), _host_f32(wf)]
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_of_block(dev, PRECISIONS[precision], c_void_p(x.data_ptr()), B, C, N, H, W, Cout, stride,
-                                    *[_f32(t) for t in host], c_void_p(y.data_ptr()), _stream_ptr(dev)), "dffw_op_of_block")
+        _check(lib.dffw_op_of_block(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, Cout, stride,
+                                    *[_f32(t) for t in host], _ptr(y), _stream_ptr(dev)), "dffw_op_of_block")
     return y
 
 
@@ -593,10 +595,9 @@ def op_pool(x, k, mode="max", precision="bf16x3"):
     B, C, N, H, W = x.shape
     y = torch.empty((B, C, N, H // k, W // k), dtype=torch.float32, device=x.device)
     x = x.contiguous()
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_pool(dev, PRECISIONS[precision], 0 if mode == "max" else 1, k, c_void_p(x.data_ptr()),
-                                B, C, N, H, W, c_void_p(y.data_ptr()), _stream_ptr(dev)), "dffw_op_pool")
+        _check(lib.dffw_op_pool(dev, PRECISIONS[precision], 0 if mode == "max" else 1, k, _ptr(x), B, C, N, H, W, _ptr(y), _stream_ptr(dev)), "dffw_op_pool")
     return y
 
 
@@ -605,10 +606,9 @@ def op_regress(score, focus_dists, H, W):
     score = score.contiguous()
     fd = focus_dists.expand(B, N, H, W)
     depth = torch.empty((B, H, W), dtype=torch.float32, device=score.device)
-    dev = score.device.index if score.device.index is not None else torch.cuda.current_device()
+    dev = _dev(score)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_regress(dev, c_void_p(score.data_ptr()), B, N, h, w, H, W, c_void_p(fd.data_ptr()),
-                                   (c_int64 * 4)(*fd.stride()), c_void_p(depth.data_ptr()), _stream_ptr(dev)),
+        _check(lib.dffw_op_regress(dev, _ptr(score), B, N, h, w, H, W, _ptr(fd), (c_int64 * 4)(*fd.stride()), _ptr(depth), _stream_ptr(dev)),
                "dffw_op_regress")
     return depth
 
@@ -627,7 +627,7 @@ def op_loss_heads(scores, focus_dists, gt, mask, conf=None, weights=(0.3, 0.5, 0
     n = len(scores)
     B, H, W = gt.shape
     N = scores[0].shape[1]
-    dev = scores[0].device.index if scores[0].device.index is not None else torch.cuda.current_device()
+    dev = _dev(scores[0])
     device = scores[0].device
     scores = [s.contiguous() for s in scores]
     for s in scores:
@@ -652,10 +652,9 @@ def op_loss_heads(scores, focus_dists, gt, mask, conf=None, weights=(0.3, 0.5, 0
     lo, hi = (0.0, 1.0) if depth_range is None else (float(depth_range[0]), float(depth_range[1]))
     with torch.cuda.device(dev):
         _check(lib.dffw_loss_heads(dev, n, ptrs(scores), (c_int * 4)(*[s.shape[2] for s in scores]), (c_int * 4)(*[s.shape[3] for s in scores]),
-                                   B, N, H, W, c_void_p(fd.data_ptr()), (c_int64 * 4)(*fd.stride()), c_void_p(gt.data_ptr()), c_void_p(mask.data_ptr()),
-                                   c_void_p(conf.data_ptr()) if conf is not None else None, (c_float * 4)(*[float(x) for x in weights[:n]]),
-                                   0 if depth_range is None else 1, lo, hi, ptrs(pred), ptrs(grad), c_void_p(losses.data_ptr()),
-                                   c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(dev)), "dffw_loss_heads")
+                                   B, N, H, W, _ptr(fd), (c_int64 * 4)(*fd.stride()), _ptr(gt), _ptr(mask), _ptr(conf),
+                                   (c_float * 4)(*[float(x) for x in weights[:n]]), 0 if depth_range is None else 1, lo, hi, ptrs(pred), ptrs(grad),
+                                   _ptr(losses), _ptr(ws), ws.numel(), _stream_ptr(dev)), "dffw_loss_heads")
     return losses, pred, grad
 
 
@@ -668,11 +667,10 @@ def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False):
     f = fovs.reshape(B, N).contiguous().float()
     out = torch.empty_like(x)
     flow = torch.empty((B, 2, N, H, W), dtype=torch.float32, device=x.device)
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _dev(x)
     with torch.cuda.device(dev):
-        _check(lib.dffw_op_fov_warp(dev, c_void_p(x.data_ptr()), B, C, N, H, W, c_void_p(a.data_ptr()), c_void_p(f.data_ptr()),
-                                    int(compat_batch_alpha0), c_void_p(out.data_ptr()), c_void_p(flow.data_ptr()),
-                                    _stream_ptr(dev)), "dffw_op_fov_warp")
+        _check(lib.dffw_op_fov_warp(dev, _ptr(x), B, C, N, H, W, _ptr(a), _ptr(f), int(compat_batch_alpha0), _ptr(out), _ptr(flow), _stream_ptr(dev)),
+               "dffw_op_fov_warp")
     return out, flow
 
 
@@ -729,7 +727,7 @@ def op_sim_render(image, depth, cams, shifts, params, *, tap=False, workspace=No
     if dev.type != "cuda" or any(t.device != dev for t in (depth, cams, shifts)):
         raise DffwError("the simulator runs on one GPU: every input must be a CUDA tensor on the same device")
     image, depth, cams, shifts = (t.contiguous() for t in (image, depth, cams, shifts))
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    idx = _dev(image)
     need = lib.dffw_sim_workspace_bytes(B, N, H, W, params.num_planes)
     ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
     out = {
@@ -741,11 +739,10 @@ def op_sim_render(image, depth, cams, shifts, params, *, tap=False, workspace=No
     }
     if tap:
         out["warped"] = torch.empty((B, N, H, W, 3), dtype=torch.float32, device=dev)
-    ptr = lambda k: c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
     with torch.cuda.device(idx):
-        _check(lib.dffw_sim_render(idx, params, c_void_p(cams.data_ptr()), c_void_p(image.data_ptr()), c_void_p(depth.data_ptr()),
-                                   c_void_p(shifts.data_ptr()), B, N, H, W, ptr("images"), ptr("defocus"), ptr("depth"), ptr("status"),
-                                   ptr("slices"), ptr("warped"), c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(idx)),
+        _check(lib.dffw_sim_render(idx, params, _ptr(cams), _ptr(image), _ptr(depth), _ptr(shifts), B, N, H, W,
+                                   *[_ptr(out.get(k)) for k in ("images", "defocus", "depth", "status", "slices", "warped")],
+                                   _ptr(ws), ws.numel(), _stream_ptr(idx)),
                "dffw_sim_render")
     return out
 

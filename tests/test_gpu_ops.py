@@ -770,6 +770,32 @@ def test_pools(eng, prec):
         bounded(eng.op_pool(x.cuda(), k, "avg", prec), eb.pool_ref64(x, k, "avg"), prec, "pool_avg<", "avg k=%d" % k)
 
 
+def test_op_kernels_survive_a_conv_and_a_pool(eng):
+    """op_conv3d and op_pool leave op_kernels() untouched: the list stays the last block op's (the data-gradient half of
+    op_conv3d_backward, an op_conv3d inside, relies on it)."""
+    B, C, N, H, W = 1, 8, 2, 8, 16
+    x = rnd(B, C, N, H, W, seed=21).cuda()
+    eng.op_srd(x, *eb.srd_params("trained_bn", C, seed=22))
+    ks = eng.op_kernels()
+    assert ks and all(k.startswith("dffw::") for k in ks), ks
+    eng.op_conv3d(x, rnd(C, C, 3, 3, 3, seed=23, scale=0.1), pad=1)
+    assert eng.op_kernels() == ks
+    eng.op_pool(x, 2)
+    assert eng.op_kernels() == ks
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
+@pytest.mark.parametrize("cin,cout", [(3, 8), (12, 16)])
+def test_conv_channel_padded_input(eng, cin, cout, prec):
+    """Cin % 8 != 0 on a layer that is not the stem: the op pads the input's channels to a multiple of 8 inside its NaN-poisoned workspace.
+    The smallest shapes at which a pad channel that is not zero reaches an output (NaN times a zero weight is NaN)."""
+    B, N, H, W = 1, 2, 8, 16
+    x = rnd(B, cin, N, H, W, seed=31)
+    w = rnd(cout, cin, 1, 3, 3, seed=32, scale=(2.0 / (cin * 9)) ** 0.5 * 1.7)
+    got = eng.op_conv3d(x.cuda(), w, pad=(0, 1, 1), precision=prec)
+    bounded(got, eb.conv_ref64(x, w, pad=(0, 1, 1)), prec, eng.last_conv_kernel(), "Cin=%d" % cin)
+
+
 def test_softplus_pointwise_sweep(eng):
     """softplus_fast (dffw_kernels.hip: log2 / rcp on the hardware transcendentals, no series, no IEEE divide) point by point instead of through a
     whole-map norm: a two-slice head with focus distances (0, 1) returns p1 / (p0 + p1), p = softplus(v) + 1e-6 (DEN.py:88-90), i.e. the RATIO of two

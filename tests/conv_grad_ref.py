@@ -1,5 +1,5 @@
-"""Reference, bounds and a CPU emulation for the conv backward; shared by tests/test_conv_grad.py and
-tests/test_gpu_conv_grad.py.
+"""Reference, bounds and a CPU emulation for the conv backward; shared by tests/test_conv_grad.py,
+tests/test_gpu_conv_grad.py and tests/test_gpu_train_records.py (which also takes the record layout helpers from here).
 
 Reference: float64 ``torch.autograd.grad`` of ``F.conv3d`` / ``F.conv_transpose3d`` on the CPU.
 
@@ -96,6 +96,26 @@ def round_parts(v, prec):
     return hi, (v - hi).bfloat16().float()
 
 
+_BITS = {"bf16x3": torch.bfloat16, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def to_records(t, prec):
+    """(B, C, N, H, W) float32 -> the activation records the library reads, an int16 tensor [B, N, H, W, parts, C]: ``[pixel][part][channel]``,
+    part 0 = hi, part 1 = lo (split-bf16 only), each the bit pattern of ``round_parts``' value.  The device's split (Fmt::split, dffw_device.h)
+    is the same round-to-nearest-even hi = bf16(v), lo = bf16(v - hi), or half(v)."""
+    parts = [p.to(_BITS[prec]).view(torch.int16).permute(0, 2, 3, 4, 1) for p in round_parts(t.detach().cpu(), prec)]
+    return torch.stack(parts, dim=4).contiguous()
+
+
+def from_records(r, prec, C):
+    """The inverse of ``to_records``: int16 records [B, N, H, W, parts, C] -> (B, C, N, H, W) float32, hi + lo."""
+    nparts = 2 if prec == "bf16x3" else 1
+    assert r.dtype == torch.int16 and r.dim() == 6 and r.shape[4] == nparts and r.shape[5] == C, (r.dtype, tuple(r.shape), prec, C)
+    v = r.detach().cpu().contiguous().view(_BITS[prec]).float()
+    v = v[..., 0, :] + v[..., 1, :] if nparts == 2 else v[..., 0, :]
+    return v.permute(0, 4, 1, 2, 3).contiguous()
+
+
 def persistent_units(total, grid_x):
     """Units of every workgroup under the rule of dffw_persist.h (persistent_range): workgroup b serves XCD b % 8, a contiguous range of the units."""
     per_xcd = grid_x // 8
@@ -107,6 +127,15 @@ def persistent_units(total, grid_x):
         end = xs + q + (1 if xcd < rem else 0)
         out.append(list(range(xs + widx, end, per_xcd)))
     return out
+
+
+def counted_units(geom, B, N, Hg, Wg, grid_x):
+    """[slice tap][workgroup] -> the units that workgroup really sums on the grid-side volume (B, N, Hg, Wg): its persistent range without the
+    units whose slice tap falls into the slice padding.  More than FLUSH_UNITS of them: the workgroup flushes a full-length fp32 partial."""
+    k, _, p, _ = GEOMETRIES[geom]
+    per_slice = -(-Hg // TY) * -(-Wg // TX)
+    upw = persistent_units(B * N * per_slice, grid_x)
+    return [[sum(0 <= (u // per_slice) % N + kz - p[0] < N for u in units) for units in upw] for kz in range(k[0])]
 
 
 def _units(t, Hg, Wg):
@@ -184,9 +213,9 @@ def emulate_wgrad(x, gy, geom, prec, *, grid_x=8, flush_units=FLUSH_UNITS, fault
     return dw.float()
 
 
-def make_case(regime, geom, B, cin, cout, N, H, W, seed):
-    """(x, w, gy) float32 CPU tensors of a regime: zero_mean, post_relu (x), offset (both), impulse (a unit-impulse gy), one_sample (gy zero
-    except in the last sample of the batch)."""
+def make_case(regime, geom, B, cin, cout, N, H, W, seed, impulse_channel=None):
+    """(x, w, gy) float32 CPU tensors of a regime: zero_mean, post_relu (x), offset (both), impulse (a unit-impulse gy, in channel
+    ``impulse_channel``; None: cout // 2), one_sample (gy zero except in the last sample of the batch)."""
     g = torch.Generator().manual_seed(seed)
     xs, ys = (B, cin, N, H, W), out_shape(geom, B, cin, cout, N, H, W)
     u = lambda shape: torch.rand(*shape, generator=g) * 2 - 1
@@ -197,7 +226,7 @@ def make_case(regime, geom, B, cin, cout, N, H, W, seed):
         x, gy = 3 + 0.5 * x, 1 + 0.25 * gy
     elif regime == "impulse":
         gy = torch.zeros(ys)
-        gy[B - 1, cout // 2, N // 2, ys[3] // 2, ys[4] - 2] = 1.0
+        gy[B - 1, cout // 2 if impulse_channel is None else impulse_channel, N // 2, ys[3] // 2, ys[4] - 2] = 1.0
     elif regime == "one_sample":   # every other sample of the batch contributes exact zeros
         gy[:B - 1] = 0.0
     kk = GEOMETRIES[geom][0]

@@ -1,4 +1,4 @@
-// Train-mode BatchNorm3d: the C ABI of the kernels of dffw_bn.hip.  The record forms enqueue on the caller's stream into the caller's
+// Train-mode BatchNorm3d and the gradient mask-and-add (§15): the C ABI of the kernels of dffw_bn.hip.  The record forms enqueue on the caller's stream into the caller's
 // workspace; the op forms (dffw_ops.cpp) convert fp32 NCDHW tensors with the from_ncdhw / to_ncdhw kernels around them.
 #include <string>
 
@@ -116,6 +116,30 @@ int dffw_bn_train_backward(int device, int precision, const void *x, const void 
         names += std::string(";") + bn_bwd_apply_kernel_name(precision, relu, grad_res != nullptr);
     }
     dffw_set_last_op_kernels(names.c_str());
+    return DFFW_OK;
+}
+
+int dffw_grad_combine(int device, int precision, const void *a, const void *y, const void *b, int B, int C, int N, int H, int W, void *out, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    if (C < 8 || C % 8 || C > 128) return fail(DFFW_EINVAL, "grad_combine needs a multiple of 8 channels up to 128, got %d", C);
+    const int64_t M = (int64_t)B * N * H * W;
+    if (M >= (1ll << 31)) return fail(DFFW_EINVAL, "volume too large: %lld pixels do not fit 31 bits", (long long)M);
+    if (!a || !out) return fail(DFFW_EINVAL, "null argument");
+    if (!y && !b) return fail(DFFW_EINVAL, "grad_combine without a mask (y) and without a second gradient (b) is a copy: not an operation");
+    if (!aligned16(a) || !aligned16(y) || !aligned16(b) || !aligned16(out)) return fail(DFFW_EINVAL, "records must be 16-byte aligned");
+    HIPCHK(hipSetDevice(device));
+    CombineArgs c;
+    c.a = (const uint16_t *)a;
+    c.y = (const uint16_t *)y;
+    c.b = (const uint16_t *)b;
+    c.out = (uint16_t *)out;
+    c.C = C;
+    c.M = (int)M;
+    c.total_units = (int)((M + bn::UNIT_PIX - 1) / bn::UNIT_PIX);
+    HIPCHK(launch_grad_combine(precision, c, Switches::read().bn_wgs, (hipStream_t)hip_stream));
+    dffw_set_last_op_kernels(grad_combine_kernel_name(precision, y != nullptr, b != nullptr));
     return DFFW_OK;
 }
 

@@ -39,6 +39,15 @@ hipError_t launch_bn_apply(int prec, int relu, int res, const BnArgs &a, int wgs
 hipError_t launch_bn_bwd_reduce(int prec, int relu, const BnArgs &a, int wgs, float *grad_gamma, float *grad_beta, hipStream_t s);
 hipError_t launch_bn_bwd_apply(int prec, int relu, int res, const BnArgs &a, int wgs, hipStream_t s);
 
+// out = [y > 0] a (+ b) on records of C channels (a multiple of 8), M pixels; y or b may be null, not both
+struct CombineArgs {
+    const uint16_t *a, *y, *b;
+    uint16_t *out;           // may alias a, y or b
+    int C, M, total_units;   // units of bn::UNIT_PIX pixels
+};
+const char *grad_combine_kernel_name(int prec, int mask, int add);   // nullptr without mask and add
+hipError_t launch_grad_combine(int prec, const CombineArgs &a, int wgs, hipStream_t s);
+
 // dffw_bn.cpp: is (B, C, N, H, W) a volume train-mode BatchNorm serves?  DFFW_OK, or the error with its message set
 int bn_train_check(int precision, int B, int C, int N, int H, int W);
 

@@ -255,6 +255,53 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnArgs a) {
     });
 }
 
+// ---- gradient mask-and-add on records: out = [y > 0] a (+ b), the ReLU mask and the fan-in sum of the convs that have no BatchNorm ----
+// One thread owns an octet of channels of a pixel (any multiple of 8 channels: the octets of a unit's pixels are dealt to the threads one by one).
+// Without b the record of a passes bit for bit (or becomes +0); with b the two record values are added in fp32 and split again.  Every thread reads
+// its octet of a, y and b before it writes that octet of out, so out may alias any of them
+template <int PREC, int MASK, int ADD>
+__global__ __launch_bounds__(256) void grad_combine_kernel(const CombineArgs a) {
+    constexpr int PARTS = Fmt<PREC>::PARTS;
+    const int no = a.C >> 3;
+    const int64_t stride = (int64_t)PARTS * a.C;
+    const UnitRange rg = persistent_range(a.total_units);
+    for (int u = rg.first; u < rg.end; u += rg.step) {
+        const int64_t p0 = (int64_t)u * UNIT_PIX;
+        const int items = (int)min((int64_t)UNIT_PIX, (int64_t)a.M - p0) * no;
+#pragma unroll 2
+        for (int j = threadIdx.x; j < items; j += 256) {
+            const int px = j / no, o = j - px * no;
+            const int64_t off = (p0 + px) * stride + o * 8;
+            float y[8];
+            if constexpr (MASK) load8<PREC>(a.y + off, a.C, y);
+            if constexpr (ADD) {
+                float v[8], w[8];
+                load8<PREC>(a.a + off, a.C, v);
+                load8<PREC>(a.b + off, a.C, w);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if constexpr (MASK) v[k] = y[k] > 0.f ? v[k] : 0.f;
+                    v[k] += w[k];
+                }
+                store8<PREC>(a.out + off, a.C, v);
+            } else {   // (MASK only: the launcher has no row without both)
+                uint32_t m[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m[k] = (y[2 * k] > 0.f ? 0xFFFFu : 0u) | (y[2 * k + 1] > 0.f ? 0xFFFF0000u : 0u);
+#pragma unroll
+                for (int part = 0; part < PARTS; ++part) {
+                    uint4 r = *reinterpret_cast<const uint4 *>(a.a + off + part * a.C);
+                    r.x &= m[0];
+                    r.y &= m[1];
+                    r.z &= m[2];
+                    r.w &= m[3];
+                    *reinterpret_cast<uint4 *>(a.out + off + part * a.C) = r;
+                }
+            }
+        }
+    }
+}
+
 using BnRow = KernelRow<BnArgs>;
 // [precision]
 static const BnRow STATS_ROWS[] = {DFFW_ROW(256, bn_stats_kernel, 0), DFFW_ROW(256, bn_stats_kernel, 1), DFFW_ROW(256, bn_stats_kernel, 2)};
@@ -315,6 +362,24 @@ hipError_t launch_bn_bwd_reduce(int prec, int relu, const BnArgs &a, int wgs, fl
 
 hipError_t launch_bn_bwd_apply(int prec, int relu, int res, const BnArgs &a, int wgs, hipStream_t s) {
     return launch_row(bwd_apply_row(prec, relu, res), a.total_units, want_of(wgs), 1, s, a);
+}
+
+using CombineRow = KernelRow<CombineArgs>;
+// [precision][mask only, add only, mask and add]
+static const CombineRow COMBINE_ROWS[] = {
+    DFFW_ROW(256, grad_combine_kernel, 0, 1, 0), DFFW_ROW(256, grad_combine_kernel, 0, 0, 1), DFFW_ROW(256, grad_combine_kernel, 0, 1, 1),
+    DFFW_ROW(256, grad_combine_kernel, 1, 1, 0), DFFW_ROW(256, grad_combine_kernel, 1, 0, 1), DFFW_ROW(256, grad_combine_kernel, 1, 1, 1),
+    DFFW_ROW(256, grad_combine_kernel, 2, 1, 0), DFFW_ROW(256, grad_combine_kernel, 2, 0, 1), DFFW_ROW(256, grad_combine_kernel, 2, 1, 1),
+};
+static const CombineRow *combine_row(int prec, int mask, int add) { return mask || add ? prec_row(COMBINE_ROWS, prec, 3, 2 * !!add + !!mask - 1) : nullptr; }
+
+const char *grad_combine_kernel_name(int prec, int mask, int add) {
+    const CombineRow *row = combine_row(prec, mask, add);
+    return row ? row->name : nullptr;
+}
+
+hipError_t launch_grad_combine(int prec, const CombineArgs &a, int wgs, hipStream_t s) {
+    return launch_row(combine_row(prec, a.y != nullptr, a.b != nullptr), a.total_units, want_of(wgs), 1, s, a);
 }
 
 }  // namespace dffw

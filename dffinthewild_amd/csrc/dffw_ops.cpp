@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "dffw_bn.h"
+#include "dffw_conv_pw_wgrad.h"
 #include "dffw_conv_wgrad.h"
 #include "dffw_run.h"
 
@@ -376,6 +377,55 @@ int dffw_op_bn_train_backward(int device, int precision, const float *x, const f
                                            grad_beta, ws, wsb, r.s);
         if (grad_x) stage_out(r, gx, grad_x);
         if (grad_res) stage_out(r, gr, grad_res);
+    });
+}
+
+// ---- the convs without in-plane taps: 3x1x1 p(1,0,0) and 1x1x1, stride 1
+int dffw_op_conv_pw_backward(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight, int Cout,
+                             const int kernel[3], const int pad[3], const float *grad_y, float *grad_x, float *grad_w, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = conv_pw_backward_check(precision, B, Cin, N, H, W, Cout, kernel, pad)) return rc;
+    if (!x || !grad_y || (grad_x && !weight)) return fail(DFFW_EINVAL, "null argument");
+    const int one[3] = {1, 1, 1};
+    if (grad_x) {   // the adjoint conv over grad_y (Cout -> Cin channels): filter flipped along the slice axis, in/out channels swapped, the same padding
+        const int kd = kernel[0];
+        std::vector<float> wa((size_t)Cin * Cout * kd);
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < Cin; ++ci)
+                for (int t = 0; t < kd; ++t) wa[((size_t)ci * Cout + co) * kd + (kd - 1 - t)] = weight[((size_t)co * Cin + ci) * kd + t];
+        const int rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, H, W, wa.data(), Cin, kernel, one, pad, one, 0, nullptr, nullptr, nullptr, 0, grad_x,
+                                      hip_stream);
+        if (rc) return rc;
+    }
+    if (!grad_w) return DFFW_OK;
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = dffw_conv_pw_wgrad_workspace_bytes(B, Cin, N, H, W, Cout, kernel, pad);
+    if (wsb <= 0) return fail(DFFW_EINVAL, "volume too large: the unit count does not fit 31 bits");
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act xa = stage_in(r, x, B, Cin, N, H, W), ya = stage_in(r, grad_y, B, Cout, N, H, W);
+        void *ws = r.raw(wsb);
+        if (real(r)) r.err = dffw_conv_pw_wgrad(device, precision, xa.p, B, Cin, N, H, W, ya.p, Cout, kernel, pad, grad_w, ws, wsb, r.s);
+    });
+}
+
+int dffw_op_grad_combine(int device, int precision, const float *a, const float *y, const float *b, int B, int C, int N, int H, int W, float *out,
+                         void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    // the record form's refusals first: nothing is staged for a call it will not take (the pointers only say which operands there are)
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    if (C < 8 || C % 8 || C > 128) return fail(DFFW_EINVAL, "grad_combine needs a multiple of 8 channels up to 128, got %d", C);
+    if ((int64_t)B * N * H * W >= (1ll << 31)) return fail(DFFW_EINVAL, "volume too large");
+    if (!a || !out) return fail(DFFW_EINVAL, "null argument");
+    if (!y && !b) return fail(DFFW_EINVAL, "grad_combine without a mask (y) and without a second gradient (b) is a copy: not an operation");
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act aa = stage_in(r, a, B, C, N, H, W), ya = y ? stage_in(r, y, B, C, N, H, W) : Act(), ba = b ? stage_in(r, b, B, C, N, H, W) : Act();
+        Act oa = r.act(B, N, H, W, C);
+        if (real(r)) r.err = dffw_grad_combine(device, precision, aa.p, ya.p, ba.p, B, C, N, H, W, oa.p, r.s);
+        stage_out(r, oa, out);
     });
 }
 

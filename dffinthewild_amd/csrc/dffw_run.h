@@ -188,6 +188,10 @@ enum SwitchId {
        accumulators sum before they are flushed (tests lower both so that one workgroup walks many units and flushes more than once) */                    \
     X(WGRAD_WGS, wgrad_wgs, 8, 0)                                                                                                                          \
     X(WGRAD_FLUSH_UNITS, wgrad_flush_units, 1, 256)                                                                                                        \
+    /* ... and the same two of the 3x1x1 / 1x1x1 weight-gradient kernel: workgroups over grid.x * grid.y, and the steps (32 pixels per     \
+       accumulator each) between two flushes, which can only be shortened (above 512: 512) */                                                             \
+    X(PWGRAD_WGS, pwgrad_wgs, 8, 0)                                                                                                                        \
+    X(PWGRAD_FLUSH_STEPS, pwgrad_flush_steps, 1, 512)                                                                                                      \
     /* train-mode BatchNorm: workgroups of each of its streaming launches (0: its default; below 8: 8, one per XCD).  Changes only the     \
        order of the float64 additions */                                                                                                                   \
     X(BN_WGS, bn_wgs, 1, 0)                                                                                                                                \

@@ -133,6 +133,14 @@ def _load():
     lib.dffw_op_bn_train.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 3 + \
                                     [c_int] + [c_void_p] * 4
     lib.dffw_op_bn_train_backward.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_int] + [c_void_p] * 5
+    lib.dffw_op_conv_pw_backward.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int,
+                                             POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.dffw_conv_pw_wgrad_workspace_bytes.argtypes = [c_int] * 6 + [POINTER(c_int)] * 2
+    lib.dffw_conv_pw_wgrad_workspace_bytes.restype = c_int64
+    lib.dffw_conv_pw_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                       POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_op_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
     return lib
 
 
@@ -155,6 +163,7 @@ ABI_SYMBOLS = (
     "dffw_loss_workspace_bytes", "dffw_loss_heads",
     "dffw_op_conv3d_backward", "dffw_conv_wgrad_workspace_bytes", "dffw_conv_wgrad",
     "dffw_bn_train_workspace_bytes", "dffw_bn_train_forward", "dffw_bn_train_backward", "dffw_op_bn_train", "dffw_op_bn_train_backward",
+    "dffw_op_conv_pw_backward", "dffw_conv_pw_wgrad_workspace_bytes", "dffw_conv_pw_wgrad", "dffw_grad_combine", "dffw_op_grad_combine",
 )
 
 
@@ -452,6 +461,62 @@ def op_conv3d_backward(x, weight, grad_y, *, stride=1, pad=0, dilation=1, transp
             raise ValueError(f"op_conv3d_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
         _check(call(gx is not None, gw is not None), "dffw_op_conv3d_backward")
     return gx, gw
+
+
+def op_conv_pw_backward(x, weight, grad_y, *, pad, stride=1, dilation=1, precision="bf16x3", need=("x", "w")):
+    """(grad_x, grad_w) of <grad_y, conv(x, weight)> for the convs without in-plane taps (dffw_op_conv_pw_backward): kernel
+    (3,1,1) with pad (1,0,0) and kernel (1,1,1) with pad 0, stride 1, no bias; channels multiples of 8 up to 128.  ``x`` (B,Cin,N,H,W) and
+    ``grad_y`` (B,Cout,N,H,W) float32 on the GPU, ``weight`` CPU/GPU float32 (Cout,Cin,kd,1,1); ``stride`` and ``dilation`` must be 1.  ``need``: which of "x", "w" to compute; the
+    other entry is None.  grad_x comes from the adjoint conv through the forward's dispatch, grad_w from the conv_pw_wgrad kernels."""
+    if x.device.type != "cuda" or grad_y.device.type != "cuda":
+        raise DffwError("op_conv_pw_backward needs GPU tensors (no CPU fallback)")
+    if tuple(_i3(stride)) != (1, 1, 1) or tuple(_i3(dilation)) != (1, 1, 1):
+        raise ValueError(f"op_conv_pw_backward: stride and dilation must be 1, got {stride} and {dilation}")
+    if x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5:
+        raise ValueError("op_conv_pw_backward: x, weight and grad_y must have 5 dimensions")
+    B, Cin, N, H, W = x.shape
+    if weight.shape[1] != Cin:
+        raise ValueError(f"op_conv_pw_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
+    Cout = weight.shape[0]
+    k, p = tuple(weight.shape[2:]), _i3(pad)
+    w = weight.detach().to("cpu", torch.float32).contiguous()
+    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
+    dev = _dev(x)
+    gx = torch.empty_like(x) if "x" in need else None
+    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
+
+    def call(with_x, with_w):
+        return lib.dffw_op_conv_pw_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), p, _ptr(grad_y),
+                                            _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        # the C entry point's own refusals first (a call with no output launches nothing), then grad_y's shape: the conv's output has x's volume
+        _check(call(False, False), "dffw_op_conv_pw_backward")
+        want = (B, Cout, N, H, W)
+        if tuple(grad_y.shape) != want:
+            raise ValueError(f"op_conv_pw_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
+        _check(call(gx is not None, gw is not None), "dffw_op_conv_pw_backward")
+    return gx, gw
+
+
+def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):
+    """``[y > 0] * a (+ b)`` on the activation records of ``precision`` (dffw_op_grad_combine): the ReLU mask of a conv that
+    has no BatchNorm, taken from the stored output ``y``, and / or the sum of two gradients of one tensor.  ``a``, ``y``, ``b`` (B,C,N,H,W)
+    float32 on the GPU, C a multiple of 8 up to 128; ``y`` and ``b`` may each be None, not both."""
+    tensors = [a] + [t for t in (y, b) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_grad_combine needs GPU tensors (no CPU fallback)")
+    if a.dim() != 5 or any(t.shape != a.shape for t in tensors):
+        raise ValueError("op_grad_combine: a, y and b must be 5-dimensional tensors of one shape")
+    if y is None and b is None:
+        raise ValueError("op_grad_combine: neither a mask (y) nor a second gradient (b): a copy is no operation")
+    B, C, N, H, W = a.shape
+    a, y, b = (t.detach().float().contiguous() if t is not None else None for t in (a, y, b))
+    dev = _dev(a)
+    out = torch.empty_like(a)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_grad_combine(dev, PRECISIONS[precision], _ptr(a), _ptr(y), _ptr(b), B, C, N, H, W, _ptr(out), _stream_ptr(dev)),
+               "dffw_op_grad_combine")
+    return out
 
 
 BN_EPS = 1e-5   # nn.BatchNorm3d's default, the value every BatchNorm of the reference network has

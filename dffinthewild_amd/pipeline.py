@@ -336,7 +336,8 @@ class HeadsLoss(torch.autograd.Function):
 # ---- conv backward: one plain conv of the aggregation network as an autograd node ----------------------------------------
 class Conv3d(torch.autograd.Function):
     """y = Conv3d.apply(x, weight, stride, pad, transposed, precision): the plain conv (no BN, bias or ReLU) through engine.op_conv3d, its
-    backward through engine.op_conv3d_backward (the adjoint conv on the forward's dispatch for x, the conv_wgrad kernels for the weight)."""
+    backward through engine.op_conv3d_backward (the adjoint conv on the forward's dispatch for x, the conv_wgrad kernels for the weight), or,
+    for the kernels (3,1,1) and (1,1,1), through engine.op_conv_pw_backward (the conv_pw_wgrad kernels)."""
 
     @staticmethod
     def forward(ctx, x, weight, stride=1, pad=0, transposed=False, precision="bf16x3"):
@@ -350,7 +351,12 @@ class Conv3d(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         stride, pad, transposed, precision = ctx.geom
         need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
-        gx, gw = engine.op_conv3d_backward(x, weight, grad_y, stride=stride, pad=pad, transposed=transposed, precision=precision, need=need)
+        if tuple(weight.shape[2:]) in ((3, 1, 1), (1, 1, 1)):
+            if transposed:
+                raise ValueError(f"conv3d backward: a transposed {tuple(weight.shape[2:])} conv is not served")
+            gx, gw = engine.op_conv_pw_backward(x, weight, grad_y, pad=pad, stride=stride, precision=precision, need=need)
+        else:
+            gx, gw = engine.op_conv3d_backward(x, weight, grad_y, stride=stride, pad=pad, transposed=transposed, precision=precision, need=need)
         if gw is not None:
             gw = gw.to(weight.device, weight.dtype)
         return gx, gw, None, None, None, None
@@ -358,7 +364,8 @@ class Conv3d(torch.autograd.Function):
 
 def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
     """conv(x, weight) on the HIP kernels with gradients for both: x (B,Cin,N,H,W) float32 CUDA, weight in PyTorch layout (CPU or CUDA).  The
-    geometries are those of engine.op_conv3d_backward, channels multiples of 8 up to 128.  With training_loss / HeadsLoss behind it a score
+    geometries are those of engine.op_conv3d_backward (3x3x3 and 1x3x3 stride 1, 3x3x3 stride (1,2,2), the transposed 3x3x3) and of
+    engine.op_conv_pw_backward (3x1x1 with pad (1,0,0) and 1x1x1, stride 1), channels multiples of 8 up to 128.  With training_loss / HeadsLoss behind it a score
     volume's gradient flows one layer further in the caller's autograd graph."""
     return Conv3d.apply(x, weight, stride, pad, transposed, precision)
 

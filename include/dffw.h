@@ -387,6 +387,32 @@ int dffw_op_bn_train_backward(int device, int precision, const float *x, const f
                               int W, const float *gamma, const float *save_mean, const float *save_invstd, int relu, float *grad_x,
                               float *grad_res, float *grad_gamma, float *grad_beta, void *hip_stream);
 
+/* ---- backward of the convs without in-plane taps, and the gradient mask-and-add between them ------------------------
+ * The attention tail of every Feature_Extraction block (Conv3d(C,C,(3,1,1), pad (1,0,0)) -> ReLU -> Conv3d(C,C,1) -> ReLU -> + Feature) and
+ * the 1x1x1 convs redir1/2/3 and pre_conv.  Geometries: kernel (3,1,1) with pad (1,0,0), kernel (1,1,1) with pad 0; stride 1, dilation 1,
+ * no bias; Cin and Cout multiples of 8 up to 128.  Anything else: DFFW_EINVAL before any launch.
+ *   grad_x   the adjoint conv (filter flipped along the slice axis, in / out channels swapped) through the forward's own dispatch
+ *   grad_w   dffw::conv_pw_wgrad_kernel + dffw::conv_pw_wgrad_finish_kernel (dffw_last_op_kernels lists them), (Cout, Cin, kd, 1, 1) fp32:
+ *            fp32 MFMA partials of at most 16 384 pixels, summed in float64 in a fixed order -- two calls give identical bits
+ * dffw_op_conv_pw_backward: x, grad_y (B,C,N,H,W) device fp32, weight host fp32 (may be NULL without grad_x), grad_x / grad_w device fp32 or
+ * NULL; allocates, poisons its workspace with 0xFF and synchronises.  dffw_conv_pw_wgrad: the enqueue-only form on activation RECORDS
+ * (16-byte aligned); workspace: dffw_conv_pw_wgrad_workspace_bytes(...) bytes, need not be cleared (0 for refused arguments; too short: DFFW_ENOMEM).
+ *
+ * dffw_grad_combine: out = [y > 0] a (+ b) on records of C channels (a multiple of 8 up to 128): the ReLU mask of a conv that has no
+ * BatchNorm, read from the STORED y, and / or the sum of two gradients of one tensor.  y and b may each be NULL, not both (DFFW_EINVAL);
+ * out may alias a, y or b.  Without b the record of a passes bit for bit where the mask passes and is +0 elsewhere; with b the two record
+ * values are added in fp32 (one rounding) and split into a record.  One launch, enqueue-only, no workspace.  dffw_op_grad_combine: the same
+ * on device fp32 tensors (B,C,N,H,W). */
+int dffw_op_conv_pw_backward(int device, int precision, const float *x, int B, int Cin, int N, int H, int W, const float *weight, int Cout,
+                             const int kernel[3], const int pad[3], const float *grad_y, float *grad_x, float *grad_w, void *hip_stream);
+int64_t dffw_conv_pw_wgrad_workspace_bytes(int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int pad[3]);
+int dffw_conv_pw_wgrad(int device, int precision, const void *x, int B, int Cin, int N, int H, int W, const void *grad_y, int Cout,
+                       const int kernel[3], const int pad[3], float *grad_w, void *workspace, int64_t workspace_bytes, void *hip_stream);
+int dffw_grad_combine(int device, int precision, const void *a, const void *y, const void *b, int B, int C, int N, int H, int W, void *out,
+                      void *hip_stream);
+int dffw_op_grad_combine(int device, int precision, const float *a, const float *y, const float *b, int B, int C, int N, int H, int W,
+                         float *out, void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

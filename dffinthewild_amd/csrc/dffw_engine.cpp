@@ -533,7 +533,7 @@ static void regress(Run &r, RegressQueue &q, const char *tag, float *score, int 
 static void flush_regress(Run &r, RegressQueue &q, int B, int N, int H, int W, const float *fd, const int64_t fst[4]) {
     if (q.hd.n && r.ok() && !r.dry) {
         q.hd.nofuse = r.sw.on(SW_NO_REGRESS_FUSED) ? 1 : 0;
-        const bool fused = q.hd.n > 1 && N <= 16 && (int64_t)B * H * W < (1ll << 31) && !q.hd.nofuse;   // launch_regress_heads' own test
+        const bool fused = regress_form(q.hd, B, N, H, W) != 0;   // launch_regress_heads' own test
         // algorithmic bytes: the score volumes and depth maps + a dense focus-distance map once (the fused kernel does read it once; per-head launches re-read it)
         const double bytes = q.bytes + ((fst[2] || fst[3]) ? (double)B * N * H * W * 4.0 : 0.0);
         r.launch_unnamed(fused ? "dffw::regress_fused_kernel" : "dffw::regress_kernel", "regress.mid_out+pred1+pred2+pred3", "", 0.0, bytes, "regress", 0,

@@ -133,6 +133,10 @@ struct RegressHeads {
     int n;
     int nofuse;   // DFFW_NO_REGRESS_FUSED (the forward's switch snapshot): one workgroup row per head (regress_kernel) instead of regress_fused_kernel
 };
+// the kernel launch_regress_heads runs for these arguments: regress_form is the fused kernel's NMAX (10, 16) or 0 for regress_kernel, regress_kernel_name
+// its symbol ("dffw::regress_fused_kernel<10>", "dffw::regress_fused_kernel<16>", "dffw::regress_kernel")
+int regress_form(const RegressHeads &hd, int B, int N, int H, int W);
+const char *regress_kernel_name(const RegressHeads &hd, int B, int N, int H, int W);
 hipError_t launch_regress_heads(const RegressHeads &hd, int B, int N, int H, int W, const float *fd, int64_t fsb, int64_t fsn, int64_t fsh,
                                 int64_t fsw, hipStream_t s);
 hipError_t launch_regress(const float *score, int B, int N, int h, int w, int H, int W, const float *fd,

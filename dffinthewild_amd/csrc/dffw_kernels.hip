@@ -1337,18 +1337,29 @@ __global__ __launch_bounds__(256) void regress_fused_kernel(const RegressHeads h
     }
 }
 
+// Which kernel launch_regress_heads runs: the fused form's NMAX (10 or 16), or 0 for regress_kernel.  The fused form (one thread = all heads of a
+// pixel) for the shapes the network produces; DFFW_NO_REGRESS_MERGE callers pass one head at a time and keep regress_kernel
+int regress_form(const RegressHeads &hd, int B, int N, int H, int W) {
+    const int64_t total = (int64_t)B * H * W;
+    if (hd.n > 1 && N <= 16 && total < (1ll << 31) && !hd.nofuse) return N <= 10 ? 10 : 16;
+    return 0;
+}
+
+const char *regress_kernel_name(const RegressHeads &hd, int B, int N, int H, int W) {
+    const int form = regress_form(hd, B, N, H, W);
+    return form == 10 ? "dffw::regress_fused_kernel<10>" : form == 16 ? "dffw::regress_fused_kernel<16>" : "dffw::regress_kernel";
+}
+
 hipError_t launch_regress_heads(const RegressHeads &hd, int B, int N, int H, int W, const float *fd, int64_t fsb, int64_t fsn, int64_t fsh,
                                 int64_t fsw, hipStream_t s) {
-    if (hd.n < 1 || hd.n > 4) return hipErrorInvalidValue;
+    if (hd.n < 1 || hd.n > 4 || B < 1 || N < 1 || H < 1 || W < 1) return hipErrorInvalidValue;   // (N < 1: the slice clamp would read in front of the scores)
+    for (int k = 0; k < hd.n; ++k)
+        if (!hd.score[k] || !hd.depth[k] || hd.h[k] < 1 || hd.w[k] < 1) return hipErrorInvalidValue;
     const int64_t total = (int64_t)B * H * W;
-    // the fused form (one thread = all heads of a pixel) for the shapes the network produces; DFFW_NO_REGRESS_MERGE callers pass one head at a time
-    // and keep regress_kernel
-    if (hd.n > 1 && N <= 16 && total < (1ll << 31) && !hd.nofuse) {
-        if (N <= 10) hipLaunchKernelGGL((regress_fused_kernel<10>), dim3(grid_for(total)), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
-        else hipLaunchKernelGGL((regress_fused_kernel<16>), dim3(grid_for(total)), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(regress_kernel, dim3(grid_for(total), (unsigned)hd.n), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
+    const int form = regress_form(hd, B, N, H, W);
+    if (form == 10) hipLaunchKernelGGL((regress_fused_kernel<10>), dim3(grid_for(total)), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
+    else if (form == 16) hipLaunchKernelGGL((regress_fused_kernel<16>), dim3(grid_for(total)), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
+    else hipLaunchKernelGGL(regress_kernel, dim3(grid_for(total), (unsigned)hd.n), dim3(256), 0, s, hd, B, N, H, W, fd, fsb, fsn, fsh, fsw);
     return hipGetLastError();
 }
 

@@ -275,12 +275,47 @@ int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, 
     });
 }
 
+// The refusals of the two regression-head entry points, before any GPU call: with N < 1 the kernels' slice clamp (N - 1) reads in front of the
+// score volume, and a size below 1 makes the tap clamp (h - 1, w - 1) negative.
+static int regress_check(int n_heads, const float *const *score, const int *h, const int *w, float *const *depth, int B, int N, int H, int W,
+                         const float *focus_dists, const int64_t *fd_strides) {
+    if (!score || !h || !w || !depth || !focus_dists || !fd_strides) return fail(DFFW_EINVAL, "null argument");
+    if (n_heads < 1 || n_heads > 4) return fail(DFFW_EINVAL, "n_heads must be 1..4, got %d", n_heads);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    for (int k = 0; k < n_heads; ++k) {
+        if (!score[k] || !depth[k]) return fail(DFFW_EINVAL, "null argument (head %d)", k);
+        if (h[k] < 1 || w[k] < 1) return fail(DFFW_EINVAL, "bad shape: head %d is %dx%d", k, h[k], w[k]);
+    }
+    return DFFW_OK;
+}
+
 int dffw_op_regress(int device, const float *score, int B, int N, int h, int w, int H, int W, const float *focus_dists,
                     const int64_t fd_strides[4], float *depth, void *hip_stream) {
-    if (!score || !focus_dists || !fd_strides || !depth) return fail(DFFW_EINVAL, "null argument");
+    if (int rc = regress_check(1, &score, &h, &w, &depth, B, N, H, W, focus_dists, fd_strides)) return rc;
     HIPCHK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(launch_regress(score, B, N, h, w, H, W, focus_dists, fd_strides[0], fd_strides[1], fd_strides[2], fd_strides[3], depth, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DFFW_OK;
+}
+
+int dffw_op_regress_heads(int device, int n_heads, const float *const score[4], const int h[4], const int w[4], float *const depth[4], int B, int N,
+                          int H, int W, const float *focus_dists, const int64_t fd_strides[4], int fused, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = regress_check(n_heads, score, h, w, depth, B, N, H, W, focus_dists, fd_strides)) return rc;
+    HIPCHK(hipSetDevice(device));
+    RegressHeads hd{};   // as regress() / flush_regress queue the forward's heads
+    hd.n = n_heads;
+    hd.nofuse = fused ? 0 : 1;
+    for (int k = 0; k < n_heads; ++k) {
+        hd.score[k] = score[k];
+        hd.depth[k] = depth[k];
+        hd.h[k] = h[k];
+        hd.w[k] = w[k];
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIPCHK(launch_regress_heads(hd, B, N, H, W, focus_dists, fd_strides[0], fd_strides[1], fd_strides[2], fd_strides[3], s));
+    dffw_set_last_op_kernels(regress_kernel_name(hd, B, N, H, W));
     HIPCHK(hipStreamSynchronize(s));
     return DFFW_OK;
 }

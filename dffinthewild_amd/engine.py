@@ -87,6 +87,8 @@ def _load():
                                      c_void_p, c_void_p, c_void_p]
     lib.dffw_op_regress.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                     POINTER(c_int64), c_void_p, c_void_p]
+    lib.dffw_op_regress_heads.argtypes = [c_int, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), POINTER(c_void_p), c_int, c_int, c_int, c_int,
+                                          c_void_p, POINTER(c_int64), c_int, c_void_p]
     c_u8p = POINTER(ctypes.c_uint8)
     lib.dffw_pack_stack.argtypes = [c_int, c_void_p, c_int, POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.dffw_augment_stack.argtypes = [c_int, c_void_p, c_int, POINTER(c_int64)] + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 6 + \
@@ -154,6 +156,7 @@ ABI_SYMBOLS = (
     "dffw_version", "dffw_last_error", "dffw_param_count", "dffw_param_info", "dffw_engine_create",
     "dffw_engine_destroy", "dffw_engine_precision", "dffw_workspace_bytes", "dffw_forward",
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
+    "dffw_op_regress_heads",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
     "dffw_op_of_block",
     "dffw_forward_raw", "dffw_pack_stack", "dffw_augment_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
@@ -651,7 +654,7 @@ def op_of_block(x, w0, bn0, w2, bn2, wf, *, stride=1, precision="bf16x3"):
 
 
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block call, in launch order."""
+    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_regress_heads call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
 
@@ -676,6 +679,38 @@ def op_regress(score, focus_dists, H, W):
         _check(lib.dffw_op_regress(dev, _ptr(score), B, N, h, w, H, W, _ptr(fd), (c_int64 * 4)(*fd.stride()), _ptr(depth), _stream_ptr(dev)),
                "dffw_op_regress")
     return depth
+
+
+def op_regress_heads(scores, focus_dists, H, W, *, fused=True, out=None):
+    """dffw_op_regress_heads: 1..4 regression heads in one launch, as the forward runs them.  scores: fp32 (B,N,h_k,w_k) CUDA tensors;
+    focus_dists broadcastable to (B,N,H,W), read through its strides as given (expanded, never copied).  fused=False: regress_kernel whatever
+    the shape (the forward under DFFW_NO_REGRESS_FUSED).  out: optional list of contiguous fp32 (B,H,W) tensors to write into.  Returns the
+    list of depth maps; op_kernels() then names the kernel launched."""
+    n = len(scores)
+    if not 1 <= n <= 4:
+        raise ValueError(f"op_regress_heads: 1 to 4 heads, got {n}")
+    B, N = scores[0].shape[:2]
+    device = scores[0].device
+    if device.type != "cuda":
+        raise DffwError("op_regress_heads needs GPU tensors (no CPU fallback)")
+    scores = [s.contiguous() for s in scores]
+    for s in scores:
+        if s.dtype != torch.float32 or s.dim() != 4 or s.shape[0] != B or s.shape[1] != N:
+            raise ValueError(f"score volumes must be float32 (B,N,h,w) with B={B}, N={N}; got {s.dtype} {tuple(s.shape)}")
+    if focus_dists.dtype != torch.float32 or focus_dists.device != device:
+        raise ValueError("focus_dists must be float32 on the scores' device")
+    fd = focus_dists.expand(B, N, H, W)
+    if out is None:
+        out = [torch.empty((B, H, W), dtype=torch.float32, device=device) for _ in range(n)]
+    if len(out) != n or any(o.dtype != torch.float32 or tuple(o.shape) != (B, H, W) or not o.is_contiguous() or o.device != device for o in out):
+        raise ValueError(f"out must be {n} contiguous float32 ({B},{H},{W}) tensors on the scores' device")
+    dev = _dev(scores[0])
+    ptrs = lambda ts: (c_void_p * 4)(*[t.data_ptr() for t in ts])
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_regress_heads(dev, n, ptrs(scores), (c_int * 4)(*[s.shape[2] for s in scores]), (c_int * 4)(*[s.shape[3] for s in scores]),
+                                         ptrs(out), B, N, H, W, _ptr(fd), (c_int64 * 4)(*fd.stride()), int(bool(fused)), _stream_ptr(dev)),
+               "dffw_op_regress_heads")
+    return list(out)
 
 
 def loss_workspace_bytes(B, N, H, W):

@@ -191,7 +191,7 @@ int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, 
                      const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y,
                      void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_op_regress_heads / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 
@@ -200,6 +200,17 @@ const char *dffw_last_op_kernels(void);
 int dffw_op_regress(int device, const float *score, int B, int N, int h, int w, int H, int W,
                     const float *focus_dists, const int64_t fd_strides[4], float *depth,
                     void *hip_stream);
+
+/* 1..4 regression heads that share the output size and the focus distances, in ONE launch, as the forward runs them: score[k] device fp32
+ * (B,N,h[k],w[k]) -> depth[k] device fp32 (B,H,W); any h[k], w[k] >= 1 (up- and downsampling).  focus_dists: device fp32 read through the
+ * element strides fd_strides (any, 0 included) of dims (B,N,H,W).  fused != 0: the forward's choice -- dffw::regress_fused_kernel<10> (N <= 10)
+ * or <16> (N <= 16) for two or more heads, dffw::regress_kernel (one workgroup row per head) otherwise; fused == 0: always dffw::regress_kernel
+ * (the forward under DFFW_NO_REGRESS_FUSED).  dffw_last_op_kernels names the kernel launched.  Every head's depth map is bit-identical to
+ * dffw_op_regress on that head alone.  Synchronises.  Both entry points refuse with DFFW_EINVAL before any GPU call: a null pointer, n_heads
+ * outside 1..4, any of B, N, H, W, h[k], w[k] below 1. */
+int dffw_op_regress_heads(int device, int n_heads, const float *const score[4], const int h[4], const int w[4],
+                          float *const depth[4], int B, int N, int H, int W, const float *focus_dists,
+                          const int64_t fd_strides[4], int fused, void *hip_stream);
 
 /* The warp operator of the End_to_End alignment path on its own.
  * Replaces FlowNetwork.FOV_warp (End_to_End/End_to_End.py:106-134): warps x (B,C,N,H,W)

@@ -840,6 +840,11 @@ def test_regression_head(eng, N, h, w, scale, layout):
     got = eng.op_regress(score.cuda(), fd_in.cuda(), H, W)
     assert rel(got, ref) <= 2e-6, rel(got, ref)
     assert float((got.cpu() - ref).abs().max()) <= 5e-6
+    # ... and every element within the per-element bound of tests/regress_ref.py (the kernel forms themselves: tests/test_gpu_regress.py)
+    import regress_ref
+    r = regress_ref.reference(score, fd_in, H, W)
+    worst = float(regress_ref.ratio(got.cpu(), r["d"], regress_ref.bound(r)).max())
+    assert worst <= 1.0, worst
 
 
 ALL3 = ("bf16x3", "fp16", "bf16")

@@ -104,6 +104,30 @@ struct Fmt {
     }
 };
 
+// ---- 16-byte record accesses of the streaming kernels (dffw_bn.hip, dffw_pool_grad.hip) ----
+// the 8 channels of one octet of one pixel: p points at the octet in the pixel's first part
+template <int PREC>
+__device__ __forceinline__ void load8(const uint16_t *p, int C, float (&v)[8]) {
+    const uint4 hi = *reinterpret_cast<const uint4 *>(p);
+    uint4 lo = make_uint4(0, 0, 0, 0);
+    if constexpr (Fmt<PREC>::PARTS == 2) lo = *reinterpret_cast<const uint4 *>(p + C);
+    Fmt<PREC>::join2(hi.x, lo.x, v[0], v[1]);
+    Fmt<PREC>::join2(hi.y, lo.y, v[2], v[3]);
+    Fmt<PREC>::join2(hi.z, lo.z, v[4], v[5]);
+    Fmt<PREC>::join2(hi.w, lo.w, v[6], v[7]);
+}
+// ... and the split of the forward epilogues (Fmt::split2) back into the parts
+template <int PREC>
+__device__ __forceinline__ void store8(uint16_t *p, int C, const float (&v)[8]) {
+    uint4 hi, lo;
+    Fmt<PREC>::split2(v[0], v[1], hi.x, lo.x);
+    Fmt<PREC>::split2(v[2], v[3], hi.y, lo.y);
+    Fmt<PREC>::split2(v[4], v[5], hi.z, lo.z);
+    Fmt<PREC>::split2(v[6], v[7], hi.w, lo.w);
+    *reinterpret_cast<uint4 *>(p) = hi;
+    if constexpr (Fmt<PREC>::PARTS == 2) *reinterpret_cast<uint4 *>(p + C) = lo;
+}
+
 template <bool F16>
 __device__ __forceinline__ f32x4 mma(short8 a, short8 b, f32x4 c) {
     if constexpr (F16)

@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -9,6 +9,7 @@
 #include "dffw_bn.h"
 #include "dffw_conv_pw_wgrad.h"
 #include "dffw_conv_wgrad.h"
+#include "dffw_pool_grad.h"
 #include "dffw_run.h"
 
 using namespace dffw;
@@ -460,6 +461,39 @@ int dffw_op_grad_combine(int device, int precision, const float *a, const float 
         Act aa = stage_in(r, a, B, C, N, H, W), ya = y ? stage_in(r, y, B, C, N, H, W) : Act(), ba = b ? stage_in(r, b, B, C, N, H, W) : Act();
         Act oa = r.act(B, N, H, W, C);
         if (real(r)) r.err = dffw_grad_combine(device, precision, aa.p, ya.p, ba.p, B, C, N, H, W, oa.p, r.s);
+        stage_out(r, oa, out);
+    });
+}
+
+// ---- backward of the pools: H and W are the pools' input resolution, g / g2 / g4 / g8 have the pooled shapes
+int dffw_op_pool_backward(int device, int precision, int mode, int k, const float *g, const float *x, const float *b, int B, int C, int N, int H, int W,
+                          float *out, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    // the record form's refusals first: nothing is staged for a call it will not take
+    if (int rc = pool_backward_check(precision, mode, k, x != nullptr, B, C, N, H, W)) return rc;
+    if (!g || !out) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act ga = stage_in(r, g, B, C, N, H / k, W / k), xa = x && mode == POOL_MAX ? stage_in(r, x, B, C, N, H, W) : Act();
+        Act ba = b ? stage_in(r, b, B, C, N, H, W) : Act(), oa = r.act(B, N, H, W, C);
+        if (real(r)) r.err = dffw_pool_backward(device, precision, mode, k, ga.p, xa.p, ba.p, B, C, N, H, W, oa.p, r.s);
+        stage_out(r, oa, out);
+    });
+}
+
+int dffw_op_pool3_backward(int device, int precision, const float *g2, const float *g4, const float *g8, const float *b, int B, int C, int N, int H, int W,
+                           float *out, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = pool3_backward_check(precision, B, C, N, H, W)) return rc;
+    if (!g2 || !g4 || !g8) return fail(DFFW_EINVAL, "the pyramid backward needs all of g2, g4 and g8");
+    if (!out) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act a2 = stage_in(r, g2, B, C, N, H / 2, W / 2), a4 = stage_in(r, g4, B, C, N, H / 4, W / 4), a8 = stage_in(r, g8, B, C, N, H / 8, W / 8);
+        Act ba = b ? stage_in(r, b, B, C, N, H, W) : Act(), oa = r.act(B, N, H, W, C);
+        if (real(r)) r.err = dffw_pool3_backward(device, precision, a2.p, a4.p, a8.p, ba.p, B, C, N, H, W, oa.p, r.s);
         stage_out(r, oa, out);
     });
 }

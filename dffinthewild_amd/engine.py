@@ -143,6 +143,10 @@ def _load():
                                        POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
     lib.dffw_op_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_pool_backward.argtypes = [c_int] * 4 + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_op_pool_backward.argtypes = [c_int] * 4 + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_pool3_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_op_pool3_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2
     return lib
 
 
@@ -167,6 +171,7 @@ ABI_SYMBOLS = (
     "dffw_op_conv3d_backward", "dffw_conv_wgrad_workspace_bytes", "dffw_conv_wgrad",
     "dffw_bn_train_workspace_bytes", "dffw_bn_train_forward", "dffw_bn_train_backward", "dffw_op_bn_train", "dffw_op_bn_train_backward",
     "dffw_op_conv_pw_backward", "dffw_conv_pw_wgrad_workspace_bytes", "dffw_conv_pw_wgrad", "dffw_grad_combine", "dffw_op_grad_combine",
+    "dffw_pool_backward", "dffw_pool3_backward", "dffw_op_pool_backward", "dffw_op_pool3_backward",
 )
 
 
@@ -519,6 +524,62 @@ def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):
     with torch.cuda.device(dev):
         _check(lib.dffw_op_grad_combine(dev, PRECISIONS[precision], _ptr(a), _ptr(y), _ptr(b), B, C, N, H, W, _ptr(out), _stream_ptr(dev)),
                "dffw_op_grad_combine")
+    return out
+
+
+POOL_MODES = {"max": 0, "avg": 1}   # dffw_op_pool's and dffw_op_pool_backward's mode
+
+
+def op_pool_backward(grad_y, x=None, b=None, *, k, mode, precision="bf16x3"):
+    """Gradient of the (1,k,k) pool's input on the activation records of ``precision`` (dffw_op_pool_backward).
+    ``grad_y`` (B,C,N,H/k,W/k) float32 on the GPU, C a multiple of 8 up to 128.  ``mode`` "max" (k = 2): ``x`` (B,C,N,H,W), the forward's
+    input, names the window's first maximum in row-major order, which receives the gradient.  ``mode`` "avg" (k = 2, 4, 8): every pixel of a
+    window receives grad_y / k^2; ``x`` is not needed.  ``b`` (B,C,N,H,W): a second gradient of the input, added in."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"op_pool_backward: mode must be one of {sorted(POOL_MODES)}, got {mode!r}")
+    tensors = [grad_y] + [t for t in (x, b) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_pool_backward needs GPU tensors (no CPU fallback)")
+    if grad_y.dim() != 5:
+        raise ValueError("op_pool_backward: grad_y must have 5 dimensions")
+    B, C, N, Ho, Wo = grad_y.shape
+    k = int(k)
+    shape = (B, C, N, Ho * k, Wo * k)
+    for t, what in ((x, "x"), (b, "b")):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"op_pool_backward: {what} {tuple(t.shape)} is not the pool's input shape {shape}")
+    grad_y, x, b = (t.detach().float().contiguous() if t is not None else None for t in (grad_y, x, b))
+    dev = _dev(grad_y)
+    out = torch.empty(shape, dtype=torch.float32, device=grad_y.device)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_pool_backward(dev, PRECISIONS[precision], POOL_MODES[mode], k, _ptr(grad_y), _ptr(x), _ptr(b), B, C, N, shape[3], shape[4],
+                                         _ptr(out), _stream_ptr(dev)), "dffw_op_pool_backward")
+    return out
+
+
+def op_pool3_backward(g2, g4, g8, b=None, *, precision="bf16x3"):
+    """Gradient of the input of the pyramid's three average pools (1,2,2), (1,4,4), (1,8,8) in one pass (dffw_op_pool3_backward, DESIGN.md
+    section 16): ``g2`` (B,C,N,H/2,W/2), ``g4`` (B,C,N,H/4,W/4), ``g8`` (B,C,N,H/8,W/8) float32 on the GPU, the gradients of the three pooled
+    volumes; ``b`` (B,C,N,H,W): a second gradient of the input, added in.  Returns ((g8 / 64 + g4 / 16) + g2 / 4) (+ b) at (B,C,N,H,W)."""
+    tensors = [g2, g4, g8] + ([b] if b is not None else [])
+    if any(t is None for t in tensors):
+        raise ValueError("op_pool3_backward needs all of g2, g4 and g8")
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_pool3_backward needs GPU tensors (no CPU fallback)")
+    if g8.dim() != 5:
+        raise ValueError("op_pool3_backward: g8 must have 5 dimensions")
+    B, C, N, H8, W8 = g8.shape
+    shape = (B, C, N, 8 * H8, 8 * W8)
+    for t, what, f in ((g2, "g2", 4), (g4, "g4", 2), (b, "b", None)):
+        want = shape if f is None else (B, C, N, f * H8, f * W8)
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"op_pool3_backward: {what} {tuple(t.shape)} does not go with g8 {tuple(g8.shape)}: expected {want}")
+    g2, g4, g8, b = (t.detach().float().contiguous() if t is not None else None for t in (g2, g4, g8, b))
+    dev = _dev(g8)
+    out = torch.empty(shape, dtype=torch.float32, device=g8.device)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_pool3_backward(dev, PRECISIONS[precision], _ptr(g2), _ptr(g4), _ptr(g8), _ptr(b), B, C, N, shape[3], shape[4], _ptr(out),
+                                          _stream_ptr(dev)), "dffw_op_pool3_backward")
     return out
 
 

@@ -402,3 +402,78 @@ def batch_norm3d(x, gamma, beta, running_mean=None, running_var=None, *, residua
     float32 CUDA with 8, 16, 32, 64 or 128 channels, gamma / beta / the running statistics CUDA tensors of C values (the running statistics
     float32, updated in place).  Behind pipeline.conv3d this is one conv -> BN -> (+skip) -> ReLU layer of the aggregation network."""
     return BatchNorm3d.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, precision)
+
+
+# ---- the pools (DESIGN.md section 16): MaxPool3d((1,2,2)), AvgPool3d((1,k,k)) and the pyramid's three average pools as autograd nodes -----------
+class MaxPool3d(torch.autograd.Function):
+    """y = MaxPool3d.apply(x, precision): the (1,2,2) max pool through engine.op_pool; the backward through engine.op_pool_backward sends each
+    gradient to its window's first maximum among the stored values of x, as torch does."""
+
+    @staticmethod
+    def forward(ctx, x, precision="bf16x3"):
+        _dev(x, "x")
+        x = x.detach().float()
+        ctx.save_for_backward(x)
+        ctx.precision = precision
+        return engine.op_pool(x, 2, "max", precision)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, = ctx.saved_tensors
+        return engine.op_pool_backward(grad_y, x=x, k=2, mode="max", precision=ctx.precision), None
+
+
+class AvgPool3d(torch.autograd.Function):
+    """y = AvgPool3d.apply(x, k, precision): the (1,k,k) average pool, k = 2, 4 or 8, through engine.op_pool and engine.op_pool_backward."""
+
+    @staticmethod
+    def forward(ctx, x, k, precision="bf16x3"):
+        _dev(x, "x")
+        ctx.cfg = (int(k), precision)
+        return engine.op_pool(x.detach().float(), int(k), "avg", precision)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        k, precision = ctx.cfg
+        return engine.op_pool_backward(grad_y, k=k, mode="avg", precision=precision), None, None
+
+
+class AvgPoolPyramid(torch.autograd.Function):
+    """p2, p4, p8 = AvgPoolPyramid.apply(x, precision): the average pools (1,2,2), (1,4,4), (1,8,8) of one volume (three engine.op_pool calls,
+    bit-identical to the forward's single pass); the backward is ONE engine.op_pool3_backward, an output without a gradient counting as zeros."""
+
+    @staticmethod
+    def forward(ctx, x, precision="bf16x3"):
+        _dev(x, "x")
+        x = x.detach().float()
+        ctx.precision = precision
+        ctx.set_materialize_grads(False)     # backward fills in the zeros itself, at the shapes it derives
+        return tuple(engine.op_pool(x, k, "avg", precision) for k in (2, 4, 8))
+
+    @staticmethod
+    def backward(ctx, g2, g4, g8):
+        return engine.op_pool3_backward(*_pyramid_grads(g2, g4, g8), precision=ctx.precision), None
+
+
+def _pyramid_grads(g2, g4, g8):
+    """The three gradients of the pyramid's outputs, zeros for one autograd did not give."""
+    given, f = next((g, f) for g, f in ((g2, 4), (g4, 2), (g8, 1)) if g is not None)
+    B, C, N, h, w = given.shape
+    H8, W8 = h // f, w // f
+    return tuple(g if g is not None else given.new_zeros((B, C, N, m * H8, m * W8)) for g, m in ((g2, 4), (g4, 2), (g8, 1)))
+
+
+def max_pool3d(x, *, precision="bf16x3"):
+    """MaxPool3d((1,2,2)) of x (B,C,N,H,W) float32 CUDA on the HIP kernels, with the gradient of x: C a multiple of 8 up to 128, H and W even."""
+    return MaxPool3d.apply(x, precision)
+
+
+def avg_pool3d(x, k, *, precision="bf16x3"):
+    """AvgPool3d((1,k,k)), k = 2, 4 or 8, of x (B,C,N,H,W) float32 CUDA on the HIP kernels, with the gradient of x."""
+    return AvgPool3d.apply(x, k, precision)
+
+
+def avg_pool_pyramid(x, *, precision="bf16x3"):
+    """(p2, p4, p8): the average pools (1,2,2), (1,4,4), (1,8,8) that hourglassup takes of one volume x (B,C,N,H,W), H and W multiples of 8,
+    with the gradient of x from one kernel launch."""
+    return AvgPoolPyramid.apply(x, precision)

@@ -424,6 +424,29 @@ int dffw_grad_combine(int device, int precision, const void *a, const void *y, c
 int dffw_op_grad_combine(int device, int precision, const float *a, const float *y, const float *b, int B, int C, int N, int H, int W,
                          float *out, void *hip_stream);
 
+/* ---- backward of the pools ---------------------------------------------------------------------------------------------
+ * The adjoints of MaxPool3d((1,2,2)) (the second branch of both res_stride_conv_3d blocks), of AvgPool3d((1,k,k)), k = 2, 4, 8, and of the
+ * pyramid's three average pools of one volume (hourglassup) in one pass.  B, C, N, H, W describe the pools' INPUT, which is where the
+ * gradient `out` is written; C a multiple of 8 up to 128, H and W divisible by k (pyramid: by 8), fewer than 2^31 pixels.
+ *   mode 0, max (k = 2)   g goes to the FIRST maximum of its 2x2 window of x in row-major order (dy, then dx), as torch does; the values
+ *                          compared are those of the stored records of x, the forward's input (-0 and +0 are equal; inputs are finite).
+ *                          Without b the record of g passes bit for bit and the other three pixels are +0.
+ *   mode 1, avg           out = g[p / k] / k^2 (exact in fp32).  x is not read.
+ *   pyramid               out = ((g8[p / 8] / 64 + g4[p / 4] / 16) + g2[p / 2] / 4), fp32 additions in this order.
+ * b, or NULL: a second gradient of the input (B,C,N,H,W), added in fp32 before the one split into a record; out may alias b.  Every element
+ * of out is written exactly once (out need not be cleared): no atomics, no workspace, identical bits from call to call and grid to grid.
+ * dffw_pool_backward / dffw_pool3_backward: on activation RECORDS (16-byte aligned), enqueue-only, one launch (dffw::pool_bwd_kernel /
+ * dffw::pool3_bwd_kernel; dffw_last_op_kernels names it), no allocation.  dffw_op_*: the same on device fp32 tensors; allocates, poisons
+ * its workspace with 0xFF and synchronises.  Anything not served is DFFW_EINVAL before any launch and before the GPU is touched. */
+int dffw_pool_backward(int device, int precision, int mode, int k, const void *g, const void *x, const void *b, int B, int C, int N, int H,
+                       int W, void *out, void *hip_stream);
+int dffw_pool3_backward(int device, int precision, const void *g2, const void *g4, const void *g8, const void *b, int B, int C, int N, int H,
+                        int W, void *out, void *hip_stream);
+int dffw_op_pool_backward(int device, int precision, int mode, int k, const float *g, const float *x, const float *b, int B, int C, int N,
+                          int H, int W, float *out, void *hip_stream);
+int dffw_op_pool3_backward(int device, int precision, const float *g2, const float *g4, const float *g8, const float *b, int B, int C, int N,
+                           int H, int W, float *out, void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

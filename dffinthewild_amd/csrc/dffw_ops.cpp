@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -11,6 +11,7 @@
 #include "dffw_conv_wgrad.h"
 #include "dffw_pool_grad.h"
 #include "dffw_run.h"
+#include "dffw_stem_wgrad.h"
 
 using namespace dffw;
 
@@ -495,6 +496,21 @@ int dffw_op_pool3_backward(int device, int precision, const float *g2, const flo
         Act ba = b ? stage_in(r, b, B, C, N, H, W) : Act(), oa = r.act(B, N, H, W, C);
         if (real(r)) r.err = dffw_pool3_backward(device, precision, a2.p, a4.p, a8.p, ba.p, B, C, N, H, W, oa.p, r.s);
         stage_out(r, oa, out);
+    });
+}
+
+// ---- backward of the stem: the weight gradient only, x is the image stack and stays fp32
+int dffw_op_stem_backward(int device, int precision, const float *x, const float *grad_y, int B, int N, int H, int W, float *grad_w, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = stem_backward_check(precision, B, N, H, W)) return rc;
+    if (!x || !grad_y || !grad_w) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = dffw_stem_wgrad_workspace_bytes(B, N, H, W);
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act ya = stage_in(r, grad_y, B, stemw::CO, N, H, W);
+        void *ws = r.raw(wsb);
+        if (real(r)) r.err = dffw_stem_wgrad(device, precision, x, ya.p, B, N, H, W, grad_w, ws, wsb, r.s);
     });
 }
 

@@ -147,6 +147,10 @@ def _load():
     lib.dffw_op_pool_backward.argtypes = [c_int] * 4 + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
     lib.dffw_pool3_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2
     lib.dffw_op_pool3_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2
+    lib.dffw_stem_wgrad_workspace_bytes.argtypes = [c_int] * 4
+    lib.dffw_stem_wgrad_workspace_bytes.restype = c_int64
+    lib.dffw_stem_wgrad.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_op_stem_backward.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]
     return lib
 
 
@@ -172,6 +176,7 @@ ABI_SYMBOLS = (
     "dffw_bn_train_workspace_bytes", "dffw_bn_train_forward", "dffw_bn_train_backward", "dffw_op_bn_train", "dffw_op_bn_train_backward",
     "dffw_op_conv_pw_backward", "dffw_conv_pw_wgrad_workspace_bytes", "dffw_conv_pw_wgrad", "dffw_grad_combine", "dffw_op_grad_combine",
     "dffw_pool_backward", "dffw_pool3_backward", "dffw_op_pool_backward", "dffw_op_pool3_backward",
+    "dffw_stem_wgrad_workspace_bytes", "dffw_stem_wgrad", "dffw_op_stem_backward",
 )
 
 
@@ -581,6 +586,33 @@ def op_pool3_backward(g2, g4, g8, b=None, *, precision="bf16x3"):
         _check(lib.dffw_op_pool3_backward(dev, PRECISIONS[precision], _ptr(g2), _ptr(g4), _ptr(g8), _ptr(b), B, C, N, shape[3], shape[4], _ptr(out),
                                           _stream_ptr(dev)), "dffw_op_pool3_backward")
     return out
+
+
+STEM_WEIGHT_SHAPE = (8, 3, 1, 9, 9)   # FM_measure.Focus_extraction.0.0: Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2), bias=False)
+STEM_GEOMETRY = dict(stride=1, pad=(0, 8, 8), dilation=(1, 2, 2))
+
+
+def op_stem_backward(x, grad_y, *, precision="bf16x3"):
+    """grad_w (8,3,1,9,9) of <grad_y, stem(x, w)> for the stem, the dilated 1x9x9 conv of the image stack (dffw_op_stem_backward, DESIGN.md
+    section 17): ``x`` (B,3,N,H,W) and ``grad_y`` (B,8,N,H,W) float32 on the GPU.  The result is a float32 GPU tensor from the stem_wgrad
+    kernels.  The stem's input is the image: there is no grad_x."""
+    if x.device.type != "cuda" or grad_y.device.type != "cuda":
+        raise DffwError("op_stem_backward needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5 or grad_y.dim() != 5:
+        raise ValueError("op_stem_backward: x and grad_y must have 5 dimensions")
+    B, Cin, N, H, W = x.shape
+    if Cin != STEM_WEIGHT_SHAPE[1]:
+        raise ValueError(f"op_stem_backward: x {tuple(x.shape)} does not have the stem's 3 input channels")
+    want = (B, STEM_WEIGHT_SHAPE[0], N, H, W)
+    if tuple(grad_y.shape) != want:
+        raise ValueError(f"op_stem_backward: grad_y {tuple(grad_y.shape)} is not the stem's output shape {want}")
+    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
+    dev = _dev(x)
+    gw = torch.empty(STEM_WEIGHT_SHAPE, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_stem_backward(dev, PRECISIONS[precision], _ptr(x), _ptr(grad_y), B, N, H, W, _ptr(gw), _stream_ptr(dev)),
+               "dffw_op_stem_backward")
+    return gw
 
 
 BN_EPS = 1e-5   # nn.BatchNorm3d's default, the value every BatchNorm of the reference network has

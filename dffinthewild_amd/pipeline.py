@@ -370,6 +370,38 @@ def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
     return Conv3d.apply(x, weight, stride, pad, transposed, precision)
 
 
+# ---- the stem: the dilated 1x9x9 conv of the image stack, with a gradient for its weight ---------------------------------
+class StemConv(torch.autograd.Function):
+    """y = StemConv.apply(x, weight, precision): FM_measure.Focus_extraction.0.0, Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2)) without
+    BN or ReLU, through engine.op_conv3d; the backward through engine.op_stem_backward (the stem_wgrad kernels) gives the weight's gradient.
+    x is the image stack and receives none."""
+
+    @staticmethod
+    def forward(ctx, x, weight, precision="bf16x3"):
+        _dev(x, "x")
+        ctx.save_for_backward(x)
+        ctx.cfg = (weight.device, weight.dtype, precision)
+        return engine.op_conv3d(x.detach().float(), weight, precision=precision, **engine.STEM_GEOMETRY)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        (x,) = ctx.saved_tensors
+        device, dtype, precision = ctx.cfg
+        gw = engine.op_stem_backward(x, grad_y, precision=precision).to(device, dtype) if ctx.needs_input_grad[1] else None
+        return None, gw, None
+
+
+def stem_conv(x, weight, *, precision="bf16x3"):
+    """The stem's conv on the HIP kernels with a gradient for ``weight``: x (B,3,N,H,W) float32 CUDA, the image stack; weight (8,3,1,9,9) in
+    PyTorch layout (CPU or CUDA).  pipeline.batch_norm3d follows it as it follows any other conv.  The data gradient of the stem is not built:
+    an ``x`` that requires grad is refused here rather than left without one."""
+    if x.requires_grad:
+        raise ValueError("stem_conv: x requires grad, but the data gradient of the stem is not built (DESIGN.md section 17: only the weight's is)")
+    if tuple(weight.shape) != engine.STEM_WEIGHT_SHAPE:
+        raise ValueError(f"stem_conv: weight {tuple(weight.shape)} is not the stem's {engine.STEM_WEIGHT_SHAPE}")
+    return StemConv.apply(x, weight, precision)
+
+
 # ---- train-mode BatchNorm (DESIGN.md section 14): BatchNorm3d with its residual add and ReLU as an autograd node -------------------------------
 class BatchNorm3d(torch.autograd.Function):
     """y = BatchNorm3d.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, precision): nn.BatchNorm3d in training

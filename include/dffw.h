@@ -447,6 +447,24 @@ int dffw_op_pool_backward(int device, int precision, int mode, int k, const floa
 int dffw_op_pool3_backward(int device, int precision, const float *g2, const float *g4, const float *g8, const float *b, int B, int C, int N,
                            int H, int W, float *out, void *hip_stream);
 
+/* ---- backward of the stem ------------------------------------------------------------------------------------------------
+ * The weight gradient of FM_measure.Focus_extraction.0.0, Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2), no bias), whose input is the
+ * image stack: there is no data gradient.
+ *   grad_w[co][ci][0][ky][kx] = sum over (b, n, y, x) of grad_y[b,co,n,y,x] * x[b,ci,n, y + 2 ky - 8, x + 2 kx - 8]   (zero outside the image)
+ *   x        device fp32 (B,3,N,H,W) contiguous, the layout dffw_op_conv3d takes for the stem; rounded to the parts of `precision` in the kernel
+ *   grad_w   (8, 3, 1, 9, 9) device fp32, by dffw::stem_wgrad_kernel + dffw::stem_wgrad_finish_kernel (dffw_last_op_kernels lists them):
+ *            fp32 MFMA partials of at most 16 384 pixels, summed in float64 in a fixed order -- two calls give identical bits
+ * dffw_stem_wgrad: enqueue-only, no allocation; grad_y an 8-channel activation RECORD [pixel][part][channel], 16-byte aligned (what
+ * dffw_bn_train_backward writes); workspace: dffw_stem_wgrad_workspace_bytes(...) bytes, need not be cleared (0 for refused arguments; too
+ * short: DFFW_ENOMEM).  dffw_op_stem_backward: grad_y (B,8,N,H,W) device fp32; allocates, poisons its workspace with 0xFF and synchronises.
+ * A null pointer, a dimension below 1, an unknown precision or 2^31 pixels and more: DFFW_EINVAL before any launch and before the GPU is
+ * touched. */
+int64_t dffw_stem_wgrad_workspace_bytes(int B, int N, int H, int W);
+int dffw_stem_wgrad(int device, int precision, const float *x, const void *grad_y, int B, int N, int H, int W, float *grad_w, void *workspace,
+                    int64_t workspace_bytes, void *hip_stream);
+int dffw_op_stem_backward(int device, int precision, const float *x, const float *grad_y, int B, int N, int H, int W, float *grad_w,
+                          void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

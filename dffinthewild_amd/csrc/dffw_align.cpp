@@ -190,11 +190,38 @@ static bool head_rows_ok(const Run &r, const std::string &hp, const PackedConv *
     return tail_sums_ok(r, c6) && c6->def.cin == y1.C && c4 && c4->def.cout == y1.C && !r.sw.on(SW_NO_HEAD_SUMS_FUSED) && r.sums_conv_ok(hp + ".4.0", y1.B, y1.N, y1.H, y1.W);
 }
 
+// the end of a head on a stored y2 (consumed): conv .6 and the plane mean, as plane sums of y2 or as the conv into three fp32 planes and
+// alpha_mean; alpha += damped head output, rawh = the undamped one
+void head_tail_stored(Run &r, const std::string &hp, const std::string &label, Act &y2, float *alpha, float *rawh) {
+    const PackedConv *c6 = r.layer(hp + ".6");
+    const int prec = r.e->prec, B = y2.B, N = y2.N;
+    const int64_t na = (int64_t)B * 3 * N, hw = (int64_t)y2.H * y2.W;
+    char kn[64];
+    if (tail_sums_ok(r, c6) && c6->def.cin == y2.C) {
+        // last conv + plane mean collapsed into plane sums of y2 (dffw_kernels.hip, "alpha head tail"): y2 is read once, the 3-plane fp32 head output is never formed
+        double *partial = (double *)r.raw((int64_t)B * N * (head_tail_chunks(B, N, hw) + 4) * y2.C * sizeof(double));
+        if (r.ok() && !r.dry) {
+            snprintf(kn, sizeof kn, "dffw::plane_sums_kernel<%d>", prec);
+            r.launch_unnamed(kn, hp, ".6+mean", 2.0 * (double)y2.pixels() * 9.0 * y2.C * 3, (double)y2.pixels() * y2.C * r.elem_bytes(), "head_tail", 0,
+                             [&](unsigned long long *) { return launch_head_tail(prec, y2.p, partial, c6->whead, alpha, rawh, B, N, y2.H, y2.W, y2.C, r.s); });
+        }
+        r.drop_raw(partial);
+        r.drop(y2);
+        return;
+    }
+    float *hf = (float *)r.raw(na * hw * sizeof(float));
+    ConvOpt of; of.outf = hf; of.outf_ch = 3;
+    r.conv(hp + ".6", y2, of);
+    r.drop(y2);
+    if (r.ok() && !r.dry)
+        r.launch_unnamed("dffw::alpha_mean_kernel", label, ".mean", 0.0, (double)na * hw * 4.0, "alpha_mean", 0, [&](unsigned long long *) { return launch_alpha_mean(hf, alpha, rawh, B, N, hw, r.s); });
+    r.drop_raw(hf);
+}
+
 // from the first conv's output y0 (consumed) through convs .2, .4, .6 and the plane mean to alpha += damped head output, rawh = the undamped one
-static void head_tail(Run &r, const std::string &hp, const std::string &label, Act &y0, float *alpha, float *rawh) {
+void head_tail(Run &r, const std::string &hp, const std::string &label, Act &y0, float *alpha, float *rawh) {
     const PackedConv *c2 = r.layer(hp + ".2.0"), *c4 = r.layer(hp + ".4.0"), *c6 = r.layer(hp + ".6");
     const int prec = r.e->prec, B = y0.B, N = y0.N;
-    const int64_t na = (int64_t)B * 3 * N, hw = (int64_t)y0.H * y0.W;
     ConvOpt rl; rl.relu = 1;
     char kn[64];
     Act y2;
@@ -247,25 +274,7 @@ static void head_tail(Run &r, const std::string &hp, const std::string &label, A
         y2 = r.conv(hp + ".4.0", y1, rl);
         r.drop(y1);
     }
-    if (tail_sums_ok(r, c6) && c6->def.cin == y2.C) {
-        // last conv + plane mean collapsed into plane sums of y2 (dffw_kernels.hip, "alpha head tail"): y2 is read once, the 3-plane fp32 head output is never formed
-        double *partial = (double *)r.raw((int64_t)B * N * (head_tail_chunks(B, N, hw) + 4) * y2.C * sizeof(double));
-        if (r.ok() && !r.dry) {
-            snprintf(kn, sizeof kn, "dffw::plane_sums_kernel<%d>", prec);
-            r.launch_unnamed(kn, hp, ".6+mean", 2.0 * (double)y2.pixels() * 9.0 * y2.C * 3, (double)y2.pixels() * y2.C * r.elem_bytes(), "head_tail", 0,
-                             [&](unsigned long long *) { return launch_head_tail(prec, y2.p, partial, c6->whead, alpha, rawh, B, N, y2.H, y2.W, y2.C, r.s); });
-        }
-        r.drop_raw(partial);
-        r.drop(y2);
-        return;
-    }
-    float *hf = (float *)r.raw(na * hw * sizeof(float));
-    ConvOpt of; of.outf = hf; of.outf_ch = 3;
-    r.conv(hp + ".6", y2, of);
-    r.drop(y2);
-    if (r.ok() && !r.dry)
-        r.launch_unnamed("dffw::alpha_mean_kernel", label, ".mean", 0.0, (double)na * hw * 4.0, "alpha_mean", 0, [&](unsigned long long *) { return launch_alpha_mean(hf, alpha, rawh, B, N, hw, r.s); });
-    r.drop_raw(hf);
+    head_tail_stored(r, hp, label, y2, alpha, rawh);
 }
 
 // One level of End_to_End.py:77-103 with the head `hp`: warps the level features `fe` (consumed) by the alpha accumulated so far, runs the

@@ -204,6 +204,7 @@ static const Table &table_for(int net) {
 std::vector<LayerDef> srd_layers(const std::string &p, int c) { Table t; t.srd(p, c); return t.layers; }
 std::vector<LayerDef> efd_layers(const std::string &p, int cin, int cout) { Table t; t.efd(p, cin, cout); return t.layers; }
 std::vector<LayerDef> of_block_layers(const std::string &p, int cin, int cout, int s) { Table t; t.of_block(p, cin, cout, s); return t.layers; }
+std::vector<LayerDef> alpha_head_layers(const std::string &p, int cin, int c) { Table t; t.alpha_head(p, cin, c); return t.layers; }
 
 }  // namespace dffw
 

@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -274,6 +274,34 @@ int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, 
             out = of_block(r, p, in);
         }
         stage_out(r, out, y);
+    });
+}
+
+// The back half of one alpha head through the graph's own head_tail() (start = 0: x is the first conv's output y0) or its end alone,
+// head_tail_stored() (start = 2: x is y2), with convs .2.0, .4.0 and .6 packed under the names of the head C selects.
+int dffw_op_head_tail(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w2, const float *bn2,
+                      const float *w4, const float *bn4, const float *w6, const float *bias6, int start, float *alpha, float *raw, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!x || !w2 || !bn2 || !w4 || !bn4 || !w6 || !bias6 || !alpha || !raw) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (C != 16 && C != 32 && C != 64) return fail(DFFW_EINVAL, "the alpha heads have 16, 32 or 64 channels, got %d", C);
+    if (start != 0 && start != 2) return fail(DFFW_EINVAL, "start must be 0 (x is y0) or 2 (x is y2), got %d", start);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    if ((int64_t)B * N * 3 > 65535) return fail(DFFW_EINVAL, "B * N * 3 = %lld planes do not fit one launch grid dimension (65535)", (long long)B * N * 3);
+    HIPCHK(hipSetDevice(device));
+    const char *head = C == 16 ? "conv3" : C == 32 ? "conv2" : "conv1";
+    const std::string hp = std::string("optical_flow_aggregation.") + head, label = std::string("flow.") + head;
+    OpEngine eng(device, precision);
+    for (const LayerDef &L : alpha_head_layers(hp, C + 2, C)) {   // as dffw_engine_create packs them; the first conv is not this op's
+        const bool l2 = L.conv == hp + ".2.0", l4 = L.conv == hp + ".4.0", l6 = L.conv == hp + ".6";
+        if (!l2 && !l4 && !l6) continue;
+        const int rc = pack_conv(L, precision, l2 ? w2 : l4 ? w4 : w6, l2 ? bn2 : l4 ? bn4 : nullptr, l6 ? bias6 : nullptr, eng.convs[L.conv]);
+        if (rc) return rc;
+    }
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act in = stage_in(r, x, B, C, N, H, W);
+        if (start == 0) head_tail(r, hp, label, in, alpha, raw);
+        else head_tail_stored(r, hp, label, in, alpha, raw);
     });
 }
 

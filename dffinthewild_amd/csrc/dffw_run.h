@@ -567,6 +567,10 @@ int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], in
 int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W, float *const out[4], float *aligned);
 Act of_block(Run &r, const std::string &p, const Act &x);
 Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W);
+// an alpha head `hp` from its first conv's output y0 (consumed) to alpha += damped plane means, rawh = the undamped ones (`label` names the
+// level in the profile); head_tail_stored: its end alone, from a stored y2 (consumed)
+void head_tail(Run &r, const std::string &hp, const std::string &label, Act &y0, float *alpha, float *rawh);
+void head_tail_stored(Run &r, const std::string &hp, const std::string &label, Act &y2, float *alpha, float *rawh);
 // the front end's blocks (dffw_engine.cpp).  srd: pooled (optional) receives max_pool(1,2,2) of the output when the fused kernel writes it on the way;
 // efd: pooled (optional) is that copy of x, at hand
 Act srd(Run &r, const std::string &p, Act &x, bool drop_x, Act *pooled = nullptr);
@@ -575,5 +579,6 @@ Act efd(Run &r, const std::string &p, const Act &x, Act *pooled = nullptr);
 std::vector<LayerDef> srd_layers(const std::string &p, int c);
 std::vector<LayerDef> efd_layers(const std::string &p, int cin, int cout);
 std::vector<LayerDef> of_block_layers(const std::string &p, int cin, int cout, int s);
+std::vector<LayerDef> alpha_head_layers(const std::string &p, int cin, int c);
 
 }  // namespace dffw

@@ -82,6 +82,7 @@ def _load():
     lib.dffw_op_srd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 6 + [c_void_p] * 3
     lib.dffw_op_efd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 4 + [c_int, c_void_p, c_void_p]
     lib.dffw_op_of_block.argtypes = [c_int, c_int, c_void_p] + [c_int] * 7 + [POINTER(c_float)] * 5 + [c_void_p] * 2
+    lib.dffw_op_head_tail.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [POINTER(c_float)] * 6 + [c_int] + [c_void_p] * 3
     lib.dffw_last_op_kernels.restype = c_char_p
     lib.dffw_op_fov_warp.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_void_p]
@@ -166,7 +167,7 @@ ABI_SYMBOLS = (
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
     "dffw_op_regress_heads",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
-    "dffw_op_of_block",
+    "dffw_op_of_block", "dffw_op_head_tail",
     "dffw_forward_raw", "dffw_pack_stack", "dffw_augment_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
@@ -746,8 +747,29 @@ def op_of_block(x, w0, bn0, w2, bn2, wf, *, stride=1, precision="bf16x3"):
     return y
 
 
+def op_head_tail(x, w2, bn2, w4, bn4, w6, bias6, alpha, raw, *, start=0, precision="bf16x3"):
+    """The back half of one alpha head (dffw_op_head_tail) through the forward's dispatch: ``x`` (B,C,N,H,W) float32 on the GPU, C = 16, 32 or
+    64, the head's first-conv output y0 (``start=0``) or its third-conv output y2 (``start=2``); weights in PyTorch layout, ``bn2`` / ``bn4`` =
+    (gamma, beta, mean, var).  ``alpha`` and ``raw``: contiguous float32 (B,3,N) GPU tensors; alpha is updated in place (+= the plane means, the
+    scale term damped by 0.001), raw receives the undamped means.  op_kernels() then lists the launches."""
+    if x.device.type != "cuda" or alpha.device != x.device or raw.device != x.device:
+        raise DffwError("op_head_tail needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5:
+        raise ValueError("op_head_tail: x must have 5 dimensions")
+    B, C, N, H, W = x.shape
+    for t, what in ((alpha, "alpha"), (raw, "raw")):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, 3, N) or not t.is_contiguous():
+            raise ValueError(f"op_head_tail: {what} must be a contiguous float32 ({B},3,{N}) tensor, got {t.dtype} {tuple(t.shape)}")
+    x = x.detach().float().contiguous()
+    host = [_host_f32(w2), _bn_host(bn2), _host_f32(w4), _bn_host(bn4), _host_f32(w6), _host_f32(bias6)]
+    dev = _dev(x)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_head_tail(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, *[_f32(t) for t in host], int(start),
+                                     _ptr(alpha), _ptr(raw), _stream_ptr(dev)), "dffw_op_head_tail")
+
+
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_regress_heads call, in launch order."""
+    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_tail / op_regress_heads call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
 

@@ -191,7 +191,19 @@ int dffw_op_of_block(int device, int precision, const float *x, int B, int Cin, 
                      const float *w0, const float *bn0, const float *w2, const float *bn2, const float *wf, float *y,
                      void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_op_regress_heads / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
+/* The back half of one alpha head of the alignment network (End_to_End.py:37-69, 86-103) through the forward's own dispatch: from the first
+ * conv's output through convs .2 and .4 (1x3x3, BatchNorm, ReLU), the biased conv .6 (C -> 3) and the plane mean to
+ *   raw[b,c,n] = m = bias6[c] + mean_{y,x} conv(y2, w6)[b,c,n],   alpha[b,c,n] += (c == 0 ? 0.001 * m : m).
+ * Test-only.  C = 16, 32 or 64 selects the head (conv3, conv2, conv1) and the layer names the weights are packed under.  x: device fp32
+ * (B,C,N,H,W): with start = 0 the first conv's output y0, with start = 2 the third conv's output y2 (only conv .6 and the mean then run,
+ * on the stored-y2 forms).  w2, w4: host fp32 (C,C,1,3,3) with bn2, bn4 (4*C values gamma|beta|mean|var); w6 (3,C,1,3,3), bias6 (3).
+ * alpha: device fp32 (B,3,N), read and updated in place; raw: device fp32 (B,3,N).  Refused with DFFW_EINVAL before any GPU call: a null
+ * pointer, an unknown precision, C outside {16, 32, 64}, start outside {0, 2}, a size below 1, B * N * 3 > 65535. */
+int dffw_op_head_tail(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w2, const float *bn2,
+                      const float *w4, const float *bn4, const float *w6, const float *bias6, int start, float *alpha, float *raw,
+                      void *hip_stream);
+
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_op_head_tail / dffw_op_regress_heads / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 

@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_grad_score.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -11,6 +11,7 @@
 #include "dffw_conv_wgrad.h"
 #include "dffw_pool_grad.h"
 #include "dffw_run.h"
+#include "dffw_score_grad.h"
 #include "dffw_stem_wgrad.h"
 
 using namespace dffw;
@@ -540,6 +541,43 @@ int dffw_op_stem_backward(int device, int precision, const float *x, const float
         void *ws = r.raw(wsb);
         if (real(r)) r.err = dffw_stem_wgrad(device, precision, x, ya.p, B, N, H, W, grad_w, ws, wsb, r.s);
     });
+}
+
+// ---- backward of the score convs, Cin -> 1: grad_score stays fp32 planar, weight is device fp32; x and b become records
+int dffw_op_score_conv_backward(int device, int precision, const float *x, int B, int Cin, int N, int h, int w, const float *weight, const int kernel[3],
+                                const int pad[3], const float *grad_score, const float *b, float *grad_x, float *grad_w, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    // the record forms' refusals first: nothing is staged for a call they will not take
+    if (int rc = score_conv_backward_check(precision, B, Cin, N, h, w, kernel, pad)) return rc;
+    if (!grad_score || (grad_x && !weight) || (grad_w && !x)) return fail(DFFW_EINVAL, "null argument");
+    if (b && !grad_x) return fail(DFFW_EINVAL, "b is added to grad_x: it needs grad_x");
+    if (!grad_x && !grad_w) return DFFW_OK;
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = grad_w ? dffw_score_conv_wgrad_workspace_bytes(B, Cin, N, h, w, kernel, pad) : 0;
+    OpEngine eng(device, precision);
+    std::string names;
+    const int rc = run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        names.clear();
+        auto note = [&] { names += (names.empty() ? "" : ";") + std::string(dffw_last_op_kernels()); };
+        if (grad_x) {
+            Act ba = b ? stage_in(r, b, B, Cin, N, h, w) : Act(), oa = r.act(B, N, h, w, Cin);
+            if (real(r)) {
+                r.err = dffw_score_conv_dgrad(device, precision, grad_score, B, Cin, N, h, w, weight, kernel, pad, ba.p, oa.p, r.s);
+                note();
+            }
+            stage_out(r, oa, grad_x);
+        }
+        if (grad_w) {
+            Act xa = stage_in(r, x, B, Cin, N, h, w);
+            void *ws = r.raw(wsb);
+            if (real(r)) {
+                r.err = dffw_score_conv_wgrad(device, precision, xa.p, grad_score, B, Cin, N, h, w, kernel, pad, grad_w, ws, wsb, r.s);
+                note();
+            }
+        }
+    });
+    dffw_set_last_op_kernels(rc == DFFW_OK ? names.c_str() : "");
+    return rc;
 }
 
 }  // extern "C"

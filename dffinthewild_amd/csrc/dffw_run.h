@@ -195,6 +195,9 @@ enum SwitchId {
     /* train-mode BatchNorm: workgroups of each of its streaming launches (0: its default; below 8: 8, one per XCD).  Changes only the     \
        order of the float64 additions */                                                                                                                   \
     X(BN_WGS, bn_wgs, 1, 0)                                                                                                                                \
+    /* backward of the score convs: workgroups of each of its launches (0: its default, 512; below 8: 8, one per XCD).  Changes only the  \
+       order of the float64 additions of the weight gradient */                                                                                           \
+    X(SCORE_WGS, score_wgs, 1, 0)                                                                                                                          \
     X(DEBUG_FLAGS, debug_flags, INT_MIN, 0)
 // ... and the two 64-bit ones (any atoll() result is taken): X(variable, field, default)
 #define DFFW_INT64_KNOBS(X)                                                                                                                                \

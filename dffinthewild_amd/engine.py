@@ -152,6 +152,11 @@ def _load():
     lib.dffw_stem_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_stem_wgrad.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_op_stem_backward.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]
+    lib.dffw_score_conv_dgrad.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, POINTER(c_int), POINTER(c_int)] + [c_void_p] * 3
+    lib.dffw_score_conv_wgrad_workspace_bytes.argtypes = [c_int] * 5 + [POINTER(c_int)] * 2
+    lib.dffw_score_conv_wgrad_workspace_bytes.restype = c_int64
+    lib.dffw_score_conv_wgrad.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 5 + [POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_op_score_conv_backward.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, POINTER(c_int), POINTER(c_int)] + [c_void_p] * 5
     return lib
 
 
@@ -178,6 +183,7 @@ ABI_SYMBOLS = (
     "dffw_op_conv_pw_backward", "dffw_conv_pw_wgrad_workspace_bytes", "dffw_conv_pw_wgrad", "dffw_grad_combine", "dffw_op_grad_combine",
     "dffw_pool_backward", "dffw_pool3_backward", "dffw_op_pool_backward", "dffw_op_pool3_backward",
     "dffw_stem_wgrad_workspace_bytes", "dffw_stem_wgrad", "dffw_op_stem_backward",
+    "dffw_score_conv_dgrad", "dffw_score_conv_wgrad_workspace_bytes", "dffw_score_conv_wgrad", "dffw_op_score_conv_backward",
 )
 
 
@@ -587,6 +593,47 @@ def op_pool3_backward(g2, g4, g8, b=None, *, precision="bf16x3"):
         _check(lib.dffw_op_pool3_backward(dev, PRECISIONS[precision], _ptr(g2), _ptr(g4), _ptr(g8), _ptr(b), B, C, N, shape[3], shape[4], _ptr(out),
                                           _stream_ptr(dev)), "dffw_op_pool3_backward")
     return out
+
+
+def op_score_conv_backward(x, weight, grad_score, *, pad, b=None, precision="bf16x3", need=("x", "w")):
+    """(grad_x, grad_w) of <grad_score, conv(x, weight)> for the convs that produce the score volumes (dffw_op_score_conv_backward, DESIGN.md
+    section 19): one output channel, kernel (1,1,1) with pad 0 or kernel (3,3,3) with pad 1, stride 1, no bias; Cin a multiple of 8 up to 128.
+    ``x`` (B,Cin,N,h,w) float32 on the GPU, ``grad_score`` (B,N,h,w) float32 on the GPU, as the loss heads write it: it stays fp32.  ``weight``
+    CPU/GPU float32 (1,Cin,k,k,k).  ``b`` (B,Cin,N,h,w): a second gradient of ``x``, added into grad_x.  ``need``: which of "x", "w" to
+    compute; the other entry is None.  Both come from the score_dgrad / score_wgrad kernels; grad_x is a record value of ``precision``."""
+    tensors = [x, grad_score] + ([b] if b is not None else [])
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError("op_score_conv_backward needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5 or weight.dim() != 5:
+        raise ValueError("op_score_conv_backward: x and weight must have 5 dimensions")
+    B, Cin, N, H, W = x.shape
+    if weight.shape[0] != 1:
+        raise ValueError(f"op_score_conv_backward: weight {tuple(weight.shape)} has {weight.shape[0]} output channels, a score conv has one")
+    if weight.shape[1] != Cin:
+        raise ValueError(f"op_score_conv_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
+    if b is not None and tuple(b.shape) != tuple(x.shape):
+        raise ValueError(f"op_score_conv_backward: b {tuple(b.shape)} is not x's shape {tuple(x.shape)}")
+    if b is not None and "x" not in need:
+        raise ValueError("op_score_conv_backward: b is added to grad_x, which is not asked for")
+    k, p = tuple(weight.shape[2:]), _i3(pad)
+    w = weight.detach().to(x.device, torch.float32).contiguous()
+    x, grad_score = x.detach().float().contiguous(), grad_score.detach().float().contiguous()
+    b = b.detach().float().contiguous() if b is not None else None
+    dev = _dev(x)
+    gx = torch.empty_like(x) if "x" in need else None
+    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
+
+    def call(with_x, with_w):
+        return lib.dffw_op_score_conv_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _ptr(w), (c_int * 3)(*k), p, _ptr(grad_score),
+                                               _ptr(b) if with_x else None, _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        # the C entry point's own refusals first (a call with no output launches nothing), then grad_score's shape: the score volume of x
+        _check(call(False, False), "dffw_op_score_conv_backward")
+        want = (B, N, H, W)
+        if tuple(grad_score.shape) != want:
+            raise ValueError(f"op_score_conv_backward: grad_score {tuple(grad_score.shape)} is not the score volume's shape {want}")
+        _check(call(gx is not None, gw is not None), "dffw_op_score_conv_backward")
+    return gx, gw
 
 
 STEM_WEIGHT_SHAPE = (8, 3, 1, 9, 9)   # FM_measure.Focus_extraction.0.0: Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2), bias=False)

@@ -370,6 +370,39 @@ def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
     return Conv3d.apply(x, weight, stride, pad, transposed, precision)
 
 
+# ---- the score convs: Cin -> 1, the convs whose outputs the loss heads read --------------------------------------------
+class ScoreConv(torch.autograd.Function):
+    """s = ScoreConv.apply(x, weight, pad, precision): a conv with ONE output channel (classif1.0 / classif2.0 / classif3.0: 1x1x1;
+    confidence.2: 3x3x3 pad 1; no bias) through engine.op_conv3d, which returns the fp32 score volume (B,N,h,w); its backward through
+    engine.op_score_conv_backward (the score_dgrad / score_wgrad kernels): the score gradient stays fp32 planar, as HeadsLoss hands it over."""
+
+    @staticmethod
+    def forward(ctx, x, weight, pad=0, precision="bf16x3"):
+        _dev(x, "x")
+        ctx.save_for_backward(x, weight)
+        ctx.geom = (pad, precision)
+        return engine.op_conv3d(x.detach().float(), weight, stride=1, pad=pad, precision=precision)
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        x, weight = ctx.saved_tensors
+        pad, precision = ctx.geom
+        need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
+        gx, gw = engine.op_score_conv_backward(x, weight, grad_score, pad=pad, precision=precision, need=need)
+        if gw is not None:
+            gw = gw.to(weight.device, weight.dtype)
+        return gx, gw, None, None
+
+
+def score_conv(x, weight, *, pad=0, precision="bf16x3"):
+    """The score volume (B,N,h,w) of a conv with one output channel, with gradients for x and weight: x (B,Cin,N,h,w) float32 CUDA, weight
+    (1,Cin,1,1,1) with pad 0 or (1,Cin,3,3,3) with pad 1 (CPU or CUDA), Cin a multiple of 8 up to 128.  With HeadsLoss behind it and conv3d /
+    batch_norm3d in front, the real head chain trains."""
+    if weight.dim() != 5 or weight.shape[0] != 1:
+        raise ValueError(f"score_conv: weight {tuple(weight.shape)} is not a conv with one output channel")
+    return ScoreConv.apply(x, weight, pad, precision)
+
+
 # ---- the stem (DESIGN.md section 17): the dilated 1x9x9 conv of the image stack, with a gradient for its weight ---------------------------------
 class StemConv(torch.autograd.Function):
     """y = StemConv.apply(x, weight, precision): FM_measure.Focus_extraction.0.0, Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2)) without

@@ -477,6 +477,34 @@ int dffw_stem_wgrad(int device, int precision, const float *x, const void *grad_
 int dffw_op_stem_backward(int device, int precision, const float *x, const float *grad_y, int B, int N, int H, int W, float *grad_w,
                           void *hip_stream);
 
+/* ---- backward of the score convs, Cin -> 1 -------------------------------------------------------------------------------
+ * The four convs that produce the fp32 score volumes dffw_loss_heads differentiates: classif1.0 / classif2.0 / classif3.0, Conv3d(Cin, 1, 1),
+ * and confidence.2, Conv3d(32, 1, 3, padding=1).  Geometries: kernel (1,1,1) with pad 0, kernel (3,3,3) with pad (1,1,1); one output channel,
+ * stride 1, dilation 1, no bias; Cin a multiple of 8 from 8 to 128; B, N, h, w >= 1 and fewer than 2^31 pixels.  Anything else, a null
+ * pointer or a misaligned one: DFFW_EINVAL before any launch and before the GPU is touched.
+ *   grad_score  device fp32 planar (B,N,h,w), exactly as dffw_loss_heads writes it (4-byte aligned); never rounded to records
+ *   weight      DEVICE fp32 (1,Cin,kd,kh,kw), PyTorch layout
+ *   grad_x[b,n,y,x,c]  = sum_k weight[c,k] grad_score[b, n+1-kz, y+1-ky, x+1-kx] (+ b[b,n,y,x,c]), taps outside the volume contribute 0.
+ *                        k111: one fp32 rounding (fmaf(w, g, b), or w * g); k333: 27 fmaf in row-major tap order from 0, then + b in fp32;
+ *                        then the one split into a record.  b, or NULL: a second gradient of the input; out may alias b.
+ *   grad_w[c,k]        = sum over (b,n,y,x) of grad_score[b,n,y,x] * x[b, n+kz-1, y+ky-1, x+kx-1, c] at the STORED record of x (hi + lo in
+ *                        split-bf16), summed in float64 (the products are exact there) per thread, workgroup and, in workgroup order, over
+ *                        the grid; device fp32 (1,Cin,kd,kh,kw).  No atomics: two calls give identical bits; DFFW_SCORE_WGS (the launches'
+ *                        workgroups, default 512) changes only the order of the float64 additions.
+ * dffw_score_conv_dgrad (dffw::score_dgrad_kernel) and dffw_score_conv_wgrad (dffw::score_wgrad_kernel + dffw::score_wgrad_finish_kernel):
+ * on activation RECORDS of Cin channels (16-byte aligned), enqueue-only, no allocation.  workspace: dffw_score_conv_wgrad_workspace_bytes(...)
+ * = grid * Cin * taps float64, 8-byte aligned, need not be cleared (0 for refused arguments; too short: DFFW_ENOMEM).
+ * dffw_op_score_conv_backward: x, b, grad_x (B,Cin,N,h,w) device fp32, grad_x / grad_w may each be NULL (with both NULL nothing is launched
+ * and only the refusals are returned); allocates, poisons its workspace with 0xFF and synchronises.  dffw_last_op_kernels lists the launches. */
+int dffw_score_conv_dgrad(int device, int precision, const float *grad_score, int B, int Cin, int N, int h, int w, const float *weight,
+                          const int kernel[3], const int pad[3], const void *b, void *out, void *hip_stream);
+int64_t dffw_score_conv_wgrad_workspace_bytes(int B, int Cin, int N, int h, int w, const int kernel[3], const int pad[3]);
+int dffw_score_conv_wgrad(int device, int precision, const void *x, const float *grad_score, int B, int Cin, int N, int h, int w,
+                          const int kernel[3], const int pad[3], float *grad_w, void *workspace, int64_t workspace_bytes, void *hip_stream);
+int dffw_op_score_conv_backward(int device, int precision, const float *x, int B, int Cin, int N, int h, int w, const float *weight,
+                                const int kernel[3], const int pad[3], const float *grad_score, const float *b, float *grad_x, float *grad_w,
+                                void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

@@ -1,5 +1,5 @@
 // Weight gradient of the convs without in-plane taps, 3x1x1 and 1x1x1: the launch contract between dffw_conv_pw_wgrad.hip
-// (kernels) and dffw_grad_pw.cpp (C ABI).
+// (kernels) and dffw_grad.cpp (C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +32,7 @@ unsigned conv_pw_wgrad_grid_x(const PwgradArgs &a, int wgs);   // persistent gri
 // conv_pw_wgrad_kernel on the persistent grid, then conv_pw_wgrad_finish_kernel: dw receives (Cg, Cf, kd, 1, 1) fp32
 hipError_t launch_conv_pw_wgrad(int prec, int kd, const PwgradArgs &a, unsigned grid_x, float *dw, hipStream_t s);
 
-// dffw_grad_pw.cpp: is this k311 / k111 on a shape the family serves?  DFFW_OK, or the error with its message set
+// dffw_grad.cpp: is this k311 / k111 on a shape the family serves?  DFFW_OK, or the error with its message set
 int conv_pw_backward_check(int precision, int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int pad[3]);
 
 }  // namespace dffw

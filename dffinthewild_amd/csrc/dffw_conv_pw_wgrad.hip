@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void conv_pw_wgrad_kernel(const PwgradArgs a) 
 
     // this lane's piece of a transposed read (conv_wgrad_kernel's map on a flat chunk): pixel 32 wave + 16 (lane >> 5) + 4 (group & 1) + q of the
     // first read, 8 pixels on for the second; channels 4p .. 4p + 3
-    const int q = (lane >> 2) & 3, p = lane & 3, half = lane >> 5, gl = (lane >> 4) & 1;
+    const auto [q, p, half, gl] = tr_lane(lane);
     const int pix0 = wave * WAVE_PIX + half * 16 + 4 * gl + q;
     const char *const ga = lds_g + pix0 * L::G_ROW + p * 8;
     const char *const fa = lds_f + pix0 * L::F_ROW + p * 8;
@@ -90,10 +90,7 @@ __global__ __launch_bounds__(256) void conv_pw_wgrad_kernel(const PwgradArgs a) 
             for (int t = 0; t < 2; ++t) {
                 if (t < nt) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        double *d = blk + (((lane >> 4) * 4 + r) * CI_G + t * 16 + (lane & 15)) * KD + kz;
-                        *d = first ? (double)acc[kz][t][r] : *d + (double)acc[kz][t][r];
-                    }
+                    for (int r = 0; r < 4; ++r) flush_f64(blk + (((lane >> 4) * 4 + r) * CI_G + t * 16 + (lane & 15)) * KD + kz, acc[kz][t][r], first);
                 }
                 acc[kz][t] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
@@ -169,11 +166,7 @@ __global__ __launch_bounds__(256) void conv_pw_wgrad_kernel(const PwgradArgs a) 
                                 const char *f0 = fs + part * L::F_PART + t * 32;
                                 bf[part] = tr_pair(f0, f0 + 8 * L::F_ROW);
                             }
-                            if constexpr (PARTS == 2) {   // the three products of every forward kernel, small ones first
-                                acc[kz][t] = mma<false>(ag[1], bf[0], acc[kz][t]);
-                                acc[kz][t] = mma<false>(ag[0], bf[1], acc[kz][t]);
-                            }
-                            acc[kz][t] = mma<PREC == P_FP16>(ag[0], bf[0], acc[kz][t]);
+                            acc[kz][t] = mma3<PREC>(ag, bf, acc[kz][t]);
                         }
                     }
                 }
@@ -234,14 +227,9 @@ unsigned conv_pw_wgrad_grid_x(const PwgradArgs &a, int wgs) {
 }
 
 hipError_t launch_conv_pw_wgrad(int prec, int kd, const PwgradArgs &a, unsigned grid_x, float *dw, hipStream_t s) {
-    const PwgradRow *row = select(prec, kd);
-    if (!row) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(row->fn, dim3(grid_x, a.ncot * a.ncig), dim3(row->block), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
     const int total = a.Cg * a.Cf * kd;
-    hipLaunchKernelGGL(conv_pw_wgrad_finish_kernel, dim3((total + 3) / 4), dim3(256), 0, s, (const double *)a.partial, (int)grid_x * 4, a.Cg, a.Cf, kd, a.ncig, dw);
-    return hipGetLastError();
+    return launch_row_then(select(prec, kd), dim3(grid_x, a.ncot * a.ncig), a, s, conv_pw_wgrad_finish_kernel, (total + 3) / 4, a.partial, (int)grid_x * 4, a.Cg,
+                           a.Cf, kd, a.ncig, dw);
 }
 
 }  // namespace dffw

@@ -10,6 +10,9 @@
 // (column tile, in-plane tap) items dealt round-robin to the waves.  Every FLUSH_UNITS units at the latest the accumulators are added, in float64,
 // into the workgroup's own block of the workspace (first flush: a plain store, so the workspace need not be cleared); conv_wgrad_finish sums the
 // workgroups' blocks in float64 in workgroup order.  No atomics anywhere: two runs give identical bits.
+//
+// The step and the flush are dffw_tr_read.h's (mma3, flush_f64).  The lane map is tr_lane()'s too, but spelled out here: through the helper the
+// stride-2 instantiations compile to other machine code than the measured one (profiles/grad_refactor_isa.txt).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 
     // this lane's piece of a transposed read: row q of the group's 4, channels 4p .. 4p + 3; the group's 4 grid points are columns
     // 8r + 4(group & 1) + 0..3 of tile row 2c + (lane >> 5) for read r of chunk c
-    const int q = (lane >> 2) & 3, p = lane & 3, half = lane >> 5, gl = (lane >> 4) & 1;
+    const int q = (lane >> 2) & 3, p = lane & 3, half = lane >> 5, gl = (lane >> 4) & 1;   // (tr_lane(): see the head of the file)
     const int col0 = 4 * gl + q;
     const char *const ga = lds_g + (half * TX + col0) * L::G_ROW + p * 8;
     const char *const fa = lds_f + (S * half * FX + S * col0) * L::F_ROW + p * 8;
@@ -73,10 +76,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
             if (item < nitems) {
                 const int t = item / 9, tap = item - t * 9;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double *d = blk + (((lane >> 4) * 4 + r) * CI_G + t * 16 + (lane & 15)) * 9 + tap;
-                    *d = first ? (double)acc[j][r] : *d + (double)acc[j][r];
-                }
+                for (int r = 0; r < 4; ++r) flush_f64(blk + (((lane >> 4) * 4 + r) * CI_G + t * 16 + (lane & 15)) * 9 + tap, acc[j][r], first);
             }
             acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -136,11 +136,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
                         const char *f0 = fa + ((S * 2 * c + ky) * FX + kx) * L::F_ROW + part * L::F_PART + t * 32;
                         bf[part] = tr_pair(f0, f0 + 8 * S * L::F_ROW);
                     }
-                    if constexpr (PARTS == 2) {   // the three products of every forward kernel, small ones first
-                        acc[j] = mma<false>(ag[1], bf[0], acc[j]);
-                        acc[j] = mma<false>(ag[0], bf[1], acc[j]);
-                    }
-                    acc[j] = mma<PREC == P_FP16>(ag[0], bf[0], acc[j]);
+                    acc[j] = mma3<PREC>(ag, bf, acc[j]);
                 }
             }
         }
@@ -186,16 +182,9 @@ unsigned conv_wgrad_grid_x(const WgradArgs &a, int wgs) {
 }
 
 hipError_t launch_conv_wgrad(int prec, int stride, const WgradArgs &a, unsigned grid_x, float *dw, hipStream_t s) {
-    const WgradRow *row = select(prec, stride);
-    if (!row) return hipErrorInvalidValue;
-    const int ny = a.kd * a.ncot * a.ncig;
-    hipLaunchKernelGGL(row->fn, dim3(grid_x, ny), dim3(row->block), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int total = a.Cg * a.Cf * a.kd * 9;
-    hipLaunchKernelGGL(conv_wgrad_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const double *)a.partial, (int)grid_x, a.Cg, a.Cf, a.kd, a.ncot,
-                       a.ncig, dw);
-    return hipGetLastError();
+    const int ny = a.kd * a.ncot * a.ncig, total = a.Cg * a.Cf * a.kd * 9;
+    return launch_row_then(select(prec, stride), dim3(grid_x, ny), a, s, conv_wgrad_finish_kernel, (total + 255) / 256, a.partial, (int)grid_x, a.Cg, a.Cf, a.kd,
+                           a.ncot, a.ncig, dw);
 }
 
 }  // namespace dffw

@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_grad_stem.cpp / dffw_grad_score.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -88,6 +88,33 @@ void stage_out(Run &r, const Act &a, float *y) {
 // ... of an fp32 score volume of n values
 void copy_out(Run &r, const float *score, float *y, int64_t n) {
     if (real(r)) r.check(hipMemcpyAsync(y, score, n * sizeof(float), hipMemcpyDeviceToDevice, r.s), "copy");
+}
+
+// the filter of the adjoint conv of a stride-1 conv (Cout, Cin, taps): every tap flipped, in and out channels swapped -> (Cin, Cout, taps)
+std::vector<float> adjoint_filter(const float *weight, int Cout, int Cin, int64_t taps) {
+    std::vector<float> wa((size_t)Cin * Cout * taps);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int64_t t = 0; t < taps; ++t) wa[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = weight[((size_t)co * Cin + ci) * taps + t];
+    return wa;
+}
+
+// A weight-gradient op: x and grad_y staged into records (a null tensor is not staged: the record form reads the op's own fp32 one), `wsb` bytes of
+// workspace, and in the real run `call(x's records, grad_y's records, workspace, stream)`, a record form of dffw_grad.cpp.  It sets
+// dffw_last_op_kernels() itself
+struct Staged {
+    const float *t;
+    int C, H, W;
+};
+int run_wgrad_op(int device, int precision, int B, int N, Staged x, Staged gy, int64_t wsb, hipStream_t s,
+                 const std::function<int(const void *, const void *, void *, hipStream_t)> &call) {
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, s, false, [&](Run &r) {
+        Act xa = x.t ? stage_in(r, x.t, B, x.C, N, x.H, x.W) : Act(), ya = gy.t ? stage_in(r, gy.t, B, gy.C, N, gy.H, gy.W) : Act();
+        void *ws = r.raw(wsb);
+        if (real(r)) r.err = call(xa.p, ya.p, ws, r.s);
+    });
 }
 
 }  // namespace
@@ -378,12 +405,8 @@ int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, in
         const int64_t taps = (int64_t)kernel[0] * 9;
         int rc;
         if (!transposed && !s2) {   // stride-1 conv of grad_y: filter flipped, in/out channels swapped, padding k - 1 - p (the same)
-            std::vector<float> wa((size_t)Cin * Cout * taps);
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci)
-                    for (int64_t t = 0; t < taps; ++t) wa[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = weight[((size_t)co * Cin + ci) * taps + t];
-            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, wa.data(), Cin, kernel, stride, pad, one, 0, nullptr, nullptr, nullptr, 0, grad_x,
-                                hip_stream);
+            rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, adjoint_filter(weight, Cout, Cin, taps).data(), Cin, kernel, stride, pad, one, 0,
+                                nullptr, nullptr, nullptr, 0, grad_x, hip_stream);
         } else {   // the stride-2 conv and the transposed conv are each other's adjoint, on the same filter
             rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, Ho, Wo, weight, Cin, kernel, stride, pad, one, s2, nullptr, nullptr, nullptr, 0,
                                 grad_x, hip_stream);
@@ -391,15 +414,11 @@ int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, in
         if (rc) return rc;
     }
     if (!grad_w) return DFFW_OK;
-    HIPCHK(hipSetDevice(device));
     const int64_t wsb = dffw_conv_wgrad_workspace_bytes(B, Cin, N, H, W, Cout, kernel, stride, pad, transposed);
-    if (wsb <= 0) return fail(DFFW_EINVAL, "volume too large: the unit count does not fit 31 bits");
-    OpEngine eng(device, precision);
-    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
-        Act xa = stage_in(r, x, B, Cin, N, H, W), ya = stage_in(r, grad_y, B, Cout, N, Ho, Wo);
-        void *ws = r.raw(wsb);
-        if (real(r)) r.err = dffw_conv_wgrad(device, precision, xa.p, B, Cin, N, H, W, ya.p, Cout, kernel, stride, pad, transposed, grad_w, ws, wsb, r.s);
-    });
+    return run_wgrad_op(device, precision, B, N, {x, Cin, H, W}, {grad_y, Cout, Ho, Wo}, wsb, (hipStream_t)hip_stream,
+                        [&](const void *xr, const void *yr, void *ws, hipStream_t s) {
+                            return dffw_conv_wgrad(device, precision, xr, B, Cin, N, H, W, yr, Cout, kernel, stride, pad, transposed, grad_w, ws, wsb, s);
+                        });
 }
 
 int dffw_op_bn_train(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *gamma, const float *beta, double eps,
@@ -454,35 +473,23 @@ int dffw_op_conv_pw_backward(int device, int precision, const float *x, int B, i
     if (!x || !grad_y || (grad_x && !weight)) return fail(DFFW_EINVAL, "null argument");
     const int one[3] = {1, 1, 1};
     if (grad_x) {   // the adjoint conv over grad_y (Cout -> Cin channels): filter flipped along the slice axis, in/out channels swapped, the same padding
-        const int kd = kernel[0];
-        std::vector<float> wa((size_t)Cin * Cout * kd);
-        for (int co = 0; co < Cout; ++co)
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int t = 0; t < kd; ++t) wa[((size_t)ci * Cout + co) * kd + (kd - 1 - t)] = weight[((size_t)co * Cin + ci) * kd + t];
-        const int rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, H, W, wa.data(), Cin, kernel, one, pad, one, 0, nullptr, nullptr, nullptr, 0, grad_x,
-                                      hip_stream);
+        const int rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, H, W, adjoint_filter(weight, Cout, Cin, kernel[0]).data(), Cin, kernel, one, pad, one, 0,
+                                      nullptr, nullptr, nullptr, 0, grad_x, hip_stream);
         if (rc) return rc;
     }
     if (!grad_w) return DFFW_OK;
-    HIPCHK(hipSetDevice(device));
     const int64_t wsb = dffw_conv_pw_wgrad_workspace_bytes(B, Cin, N, H, W, Cout, kernel, pad);
-    if (wsb <= 0) return fail(DFFW_EINVAL, "volume too large: the unit count does not fit 31 bits");
-    OpEngine eng(device, precision);
-    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
-        Act xa = stage_in(r, x, B, Cin, N, H, W), ya = stage_in(r, grad_y, B, Cout, N, H, W);
-        void *ws = r.raw(wsb);
-        if (real(r)) r.err = dffw_conv_pw_wgrad(device, precision, xa.p, B, Cin, N, H, W, ya.p, Cout, kernel, pad, grad_w, ws, wsb, r.s);
-    });
+    return run_wgrad_op(device, precision, B, N, {x, Cin, H, W}, {grad_y, Cout, H, W}, wsb, (hipStream_t)hip_stream,
+                        [&](const void *xr, const void *yr, void *ws, hipStream_t s) {
+                            return dffw_conv_pw_wgrad(device, precision, xr, B, Cin, N, H, W, yr, Cout, kernel, pad, grad_w, ws, wsb, s);
+                        });
 }
 
 int dffw_op_grad_combine(int device, int precision, const float *a, const float *y, const float *b, int B, int C, int N, int H, int W, float *out,
                          void *hip_stream) {
     dffw_set_last_op_kernels("");
     // the record form's refusals first: nothing is staged for a call it will not take (the pointers only say which operands there are)
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
-    if (C < 8 || C % 8 || C > 128) return fail(DFFW_EINVAL, "grad_combine needs a multiple of 8 channels up to 128, got %d", C);
-    if ((int64_t)B * N * H * W >= (1ll << 31)) return fail(DFFW_EINVAL, "volume too large");
+    if (int rc = check_volume("grad_combine", precision, B, N, H, W, {C}, 1, (int64_t)B * N * H * W, "pixels")) return rc;
     if (!a || !out) return fail(DFFW_EINVAL, "null argument");
     if (!y && !b) return fail(DFFW_EINVAL, "grad_combine without a mask (y) and without a second gradient (b) is a copy: not an operation");
     HIPCHK(hipSetDevice(device));
@@ -533,14 +540,9 @@ int dffw_op_stem_backward(int device, int precision, const float *x, const float
     dffw_set_last_op_kernels("");
     if (int rc = stem_backward_check(precision, B, N, H, W)) return rc;
     if (!x || !grad_y || !grad_w) return fail(DFFW_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(device));
     const int64_t wsb = dffw_stem_wgrad_workspace_bytes(B, N, H, W);
-    OpEngine eng(device, precision);
-    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
-        Act ya = stage_in(r, grad_y, B, stemw::CO, N, H, W);
-        void *ws = r.raw(wsb);
-        if (real(r)) r.err = dffw_stem_wgrad(device, precision, x, ya.p, B, N, H, W, grad_w, ws, wsb, r.s);
-    });
+    return run_wgrad_op(device, precision, B, N, {}, {grad_y, stemw::CO, H, W}, wsb, (hipStream_t)hip_stream,
+                        [&](const void *, const void *yr, void *ws, hipStream_t s) { return dffw_stem_wgrad(device, precision, x, yr, B, N, H, W, grad_w, ws, wsb, s); });
 }
 
 // ---- backward of the score convs, Cin -> 1: grad_score stays fp32 planar, weight is device fp32; x and b become records
@@ -553,29 +555,24 @@ int dffw_op_score_conv_backward(int device, int precision, const float *x, int B
     if (b && !grad_x) return fail(DFFW_EINVAL, "b is added to grad_x: it needs grad_x");
     if (!grad_x && !grad_w) return DFFW_OK;
     HIPCHK(hipSetDevice(device));
-    const int64_t wsb = grad_w ? dffw_score_conv_wgrad_workspace_bytes(B, Cin, N, h, w, kernel, pad) : 0;
-    OpEngine eng(device, precision);
-    std::string names;
-    const int rc = run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
-        names.clear();
-        auto note = [&] { names += (names.empty() ? "" : ";") + std::string(dffw_last_op_kernels()); };
-        if (grad_x) {
+    std::string names;   // of both halves, data gradient first
+    int rc = DFFW_OK;
+    if (grad_x) {
+        OpEngine eng(device, precision);
+        rc = run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
             Act ba = b ? stage_in(r, b, B, Cin, N, h, w) : Act(), oa = r.act(B, N, h, w, Cin);
-            if (real(r)) {
-                r.err = dffw_score_conv_dgrad(device, precision, grad_score, B, Cin, N, h, w, weight, kernel, pad, ba.p, oa.p, r.s);
-                note();
-            }
+            if (real(r)) r.err = dffw_score_conv_dgrad(device, precision, grad_score, B, Cin, N, h, w, weight, kernel, pad, ba.p, oa.p, r.s);
             stage_out(r, oa, grad_x);
-        }
-        if (grad_w) {
-            Act xa = stage_in(r, x, B, Cin, N, h, w);
-            void *ws = r.raw(wsb);
-            if (real(r)) {
-                r.err = dffw_score_conv_wgrad(device, precision, xa.p, grad_score, B, Cin, N, h, w, kernel, pad, grad_w, ws, wsb, r.s);
-                note();
-            }
-        }
-    });
+        });
+        names = dffw_last_op_kernels();
+    }
+    if (grad_w && rc == DFFW_OK) {
+        const int64_t wsb = dffw_score_conv_wgrad_workspace_bytes(B, Cin, N, h, w, kernel, pad);
+        rc = run_wgrad_op(device, precision, B, N, {x, Cin, h, w}, {}, wsb, (hipStream_t)hip_stream, [&](const void *xr, const void *, void *ws, hipStream_t s) {
+            return dffw_score_conv_wgrad(device, precision, xr, grad_score, B, Cin, N, h, w, kernel, pad, grad_w, ws, wsb, s);
+        });
+        names += (names.empty() ? "" : ";") + std::string(dffw_last_op_kernels());
+    }
     dffw_set_last_op_kernels(rc == DFFW_OK ? names.c_str() : "");
     return rc;
 }

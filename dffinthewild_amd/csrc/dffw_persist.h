@@ -71,6 +71,17 @@ inline hipError_t launch_row(const KernelRow<A...> *row, int total_tiles, int wa
     return hipGetLastError();
 }
 
+// a reducing family's launch: `row` on `grid`, then its finish kernel on `fgrid` blocks of 256 threads; the first error of the two
+template <class Args, class... F, class... B>
+inline hipError_t launch_row_then(const KernelRow<Args> *row, dim3 grid, const Args &a, hipStream_t s, void (*finish)(F...), unsigned fgrid, const B &...fargs) {
+    if (!row) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(row->fn, grid, dim3(row->block), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(finish, dim3(fgrid), dim3(256), 0, s, fargs...);
+    return hipGetLastError();
+}
+
 struct UnitRange {
     int first, end, step;   // this workgroup's units: first, first + step, ... below end (first >= end: nothing to do)
 };

@@ -8,17 +8,6 @@ using namespace dffw;
 
 namespace {
 
-// what both forms share; H and W are the input resolution, `div` what they must be multiples of
-int check_volume(const char *what, int precision, int B, int C, int N, int H, int W, int div) {
-    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
-    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
-    if (C < 8 || C % 8 || C > 128) return fail(DFFW_EINVAL, "%s needs a multiple of 8 channels up to 128, got %d", what, C);
-    if (H % div || W % div) return fail(DFFW_EINVAL, "%s needs H and W divisible by %d, got %dx%d", what, div, H, W);
-    const int64_t M = (int64_t)B * N * H * W;
-    if (M >= (1ll << 31)) return fail(DFFW_EINVAL, "volume too large: %lld pixels do not fit 31 bits", (long long)M);
-    return DFFW_OK;
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int units_of(int64_t M) { return (int)((M + bn::UNIT_PIX - 1) / bn::UNIT_PIX); }
@@ -29,13 +18,13 @@ int dffw::pool_backward_check(int precision, int mode, int k, bool has_x, int B,
     if (mode != POOL_MAX && mode != POOL_AVG) return fail(DFFW_EINVAL, "unknown pool mode %d (0 max, 1 average)", mode);
     if (mode == POOL_MAX && k != 2) return fail(DFFW_EINVAL, "the max pool backward serves (1,2,2) only, got k = %d", k);
     if (mode == POOL_AVG && k != 2 && k != 4 && k != 8) return fail(DFFW_EINVAL, "the average pool backward serves k = 2, 4, 8, got %d", k);
-    if (int rc = check_volume("pool backward", precision, B, C, N, H, W, k)) return rc;
+    if (int rc = check_volume("pool backward", precision, B, N, H, W, {C}, k, (int64_t)B * N * H * W, "pixels")) return rc;
     if (mode == POOL_MAX && !has_x) return fail(DFFW_EINVAL, "the max pool backward reads the argmax from x, the stored input of the forward");
     return DFFW_OK;
 }
 
 int dffw::pool3_backward_check(int precision, int B, int C, int N, int H, int W) {
-    return check_volume("the pyramid backward", precision, B, C, N, H, W, 8);
+    return check_volume("the pyramid backward", precision, B, N, H, W, {C}, 8, (int64_t)B * N * H * W, "pixels");   // H and W: the input resolution
 }
 
 extern "C" {

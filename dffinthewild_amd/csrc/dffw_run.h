@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -26,6 +27,11 @@ extern "C" char **environ;
 namespace dffw {
 
 static constexpr auto &fail = dffw_fail;
+// The shape refusals every backward family shares (defined in dffw_grad.cpp), in this order: precision, a dimension below 1, a channel count that
+// is no multiple of 8 from 8 to 128 (`channels`: {Cin, Cout}, {C}, or {} for a family with fixed channels), H or W no multiple of `div`, and
+// `units` -- the largest count the family's kernels hold in an int, from the family's own unit size -- beyond 31 bits.  DFFW_OK, or the error set
+int check_volume(const char *family, int precision, int B, int N, int H, int W, std::initializer_list<int> channels, int div, int64_t units, const char *unit);
+
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \

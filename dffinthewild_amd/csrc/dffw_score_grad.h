@@ -1,4 +1,4 @@
-// Backward of the score convs, Cin -> 1: the launch contract between dffw_score_grad.hip (kernels) and dffw_grad_score.cpp (C ABI).
+// Backward of the score convs, Cin -> 1: the launch contract between dffw_score_grad.hip (kernels) and dffw_grad.cpp (C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +35,7 @@ hipError_t launch_score_dgrad(int prec, int k, const ScoreArgs &a, int wgs, hipS
 // score_wgrad_kernel + score_wgrad_finish_kernel: grad_w (1,C,k,k,k) fp32
 hipError_t launch_score_wgrad(int prec, int k, const ScoreArgs &a, int wgs, float *grad_w, hipStream_t s);
 
-// dffw_grad_score.cpp: is this a score conv the backward serves?  DFFW_OK, or the error with its message set
+// dffw_grad.cpp: is this a score conv the backward serves?  DFFW_OK, or the error with its message set
 int score_conv_backward_check(int precision, int B, int Cin, int N, int H, int W, const int kernel[3], const int pad[3]);
 
 }  // namespace dffw

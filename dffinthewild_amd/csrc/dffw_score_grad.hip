@@ -358,12 +358,9 @@ hipError_t launch_score_dgrad(int prec, int k, const ScoreArgs &a, int wgs, hipS
 }
 
 hipError_t launch_score_wgrad(int prec, int k, const ScoreArgs &a, int wgs, float *grad_w, hipStream_t s) {
-    hipError_t e = launch_row(wgrad_row(prec, k), a.total_units, want_of(wgs), 1, s, a);
-    if (e != hipSuccess) return e;
+    const unsigned grid = score_grid(a.total_units, wgs);
     const int taps = k * k * k;
-    hipLaunchKernelGGL(score_wgrad_finish_kernel, dim3(taps * a.C / 4), dim3(256), 0, s, (const double *)a.partial, (int)score_grid(a.total_units, wgs), a.C, taps,
-                       grad_w);
-    return hipGetLastError();
+    return launch_row_then(wgrad_row(prec, k), dim3(grid), a, s, score_wgrad_finish_kernel, taps * a.C / 4, a.partial, (int)grid, a.C, taps, grad_w);
 }
 
 }  // namespace dffw

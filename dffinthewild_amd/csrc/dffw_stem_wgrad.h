@@ -1,5 +1,5 @@
 // Weight gradient of the stem, the dilated 1x9x9 conv of the image stack: the launch contract between dffw_stem_wgrad.hip
-// (kernels) and dffw_grad_stem.cpp (C ABI).
+// (kernels) and dffw_grad.cpp (C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +32,7 @@ unsigned stem_wgrad_grid_x(const StemWgradArgs &a, int wgs);   // persistent gri
 // stem_wgrad_kernel on the persistent grid, then stem_wgrad_finish_kernel: dw receives (8, 3, 1, 9, 9) fp32
 hipError_t launch_stem_wgrad(int prec, const StemWgradArgs &a, unsigned grid_x, float *dw, hipStream_t s);
 
-// dffw_grad_stem.cpp: DFFW_OK, or the error with its message set
+// dffw_grad.cpp: DFFW_OK, or the error with its message set
 int stem_backward_check(int precision, int B, int N, int H, int W);
 
 }  // namespace dffw

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
 
     // the row operand, as conv_wgrad_kernel reads it: this lane addresses pixel q of the group's 4, channels 4p .. 4p + 3; the group's 4 pixels
     // are columns 16 ch + 8r + 4 gl + 0..3 of tile row 2 cr + half for read r of chunk (cr, ch)
-    const int q = (lane >> 2) & 3, p = lane & 3, half = lane >> 5, gl = (lane >> 4) & 1;
+    const auto [q, p, half, gl] = tr_lane(lane);
     const char *const ga = lds_g + (half * TX + 4 * gl + q) * L::G_ROW + p * 8;
     // the column operand: this lane's column of each of its tiles and the element offset of its 4 pixels of read 0 of chunk (0, 0).  A dead
     // column (the last 13 of tile 15) reads filter element 0's pixels and is never flushed
@@ -76,10 +76,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
             const int col = (wave + 4 * j) * 16 + (lane & 15);
             if (col < COLS && lane < 32) {   // rows 0 .. 7 of the 16 are g's channels
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double *d = blk + ((lane >> 4) * 4 + r) * COLS + col;
-                    *d = first ? (double)acc[j][r] : *d + (double)acc[j][r];
-                }
+                for (int r = 0; r < 4; ++r) flush_f64(blk + ((lane >> 4) * 4 + r) * COLS + col, acc[j][r], first);
             }
             acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -153,11 +150,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
                         const short4v lo4 = *reinterpret_cast<const short4v *>(x0), hi4 = *reinterpret_cast<const short4v *>(x0 + 8);
                         bx[part] = short8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
                     }
-                    if constexpr (PARTS == 2) {   // the three products of every forward kernel, small ones first
-                        acc[j] = mma<false>(ag[1], bx[0], acc[j]);
-                        acc[j] = mma<false>(ag[0], bx[1], acc[j]);
-                    }
-                    acc[j] = mma<PREC == P_FP16>(ag[0], bx[0], acc[j]);
+                    acc[j] = mma3<PREC>(ag, bx, acc[j]);
                 }
             }
         }
@@ -187,13 +180,7 @@ const char *stem_wgrad_kernel_name(int prec) {
 unsigned stem_wgrad_grid_x(const StemWgradArgs &a, int wgs) { return persistent_grid(a.total_units, std::max(8, wgs > 0 ? wgs : DEFAULT_WGS)); }
 
 hipError_t launch_stem_wgrad(int prec, const StemWgradArgs &a, unsigned grid_x, float *dw, hipStream_t s) {
-    const StemWgradRow *row = prec_row(STEM_WGRAD_ROWS, prec, 1, 0);
-    if (!row) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(row->fn, dim3(grid_x), dim3(row->block), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3((BLOCK + 255) / 256), dim3(256), 0, s, (const double *)a.partial, (int)grid_x, dw);
-    return hipGetLastError();
+    return launch_row_then(prec_row(STEM_WGRAD_ROWS, prec, 1, 0), dim3(grid_x), a, s, stem_wgrad_finish_kernel, (BLOCK + 255) / 256, a.partial, (int)grid_x, dw);
 }
 
 }  // namespace dffw

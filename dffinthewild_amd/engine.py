@@ -8,6 +8,7 @@ come from its caching allocator) and for the current HIP stream, nothing else.
 import ctypes
 import os
 import threading
+import types
 from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch
@@ -447,40 +448,51 @@ def conv3d_output_shape(x_shape, weight_shape, stride, pad, transposed):
     return (B, weight_shape[0], N + 2 * p[0] - (k[0] - 1), (H + 2 * p[1] - k[1]) // s[1] + 1, (W + 2 * p[2] - k[2]) // s[2] + 1)
 
 
+def _conv_backward(fn, x, weight, grad, need, precision, *, checks, layout, want, what, b=None, weight_on_gpu=False):
+    """The body the (grad_x, grad_w) wrappers share.  ``fn``: the C entry point, whose name less ``dffw_`` is the wrapper's.  ``checks``: the
+    wrapper's own argument checks, in order, each a callable that returns a message (-> ValueError) or None.  ``layout(t)``: the C arguments
+    between the precision and the stream, from the pointers ``t.x, t.w, t.grad, t.b, t.gx, t.gw`` and the shape ``t.B, t.Cin, t.N, t.H, t.W``.
+    ``want()``: the shape ``grad`` (``what`` it is, for the message) must have; it is compared after the library's own refusals."""
+    name = fn.__name__[len("dffw_"):]
+    if any(t.device.type != "cuda" for t in (x, grad, b) if t is not None):
+        raise DffwError(f"{name} needs GPU tensors (no CPU fallback)")
+    for check in checks:
+        msg = check()
+        if msg:
+            raise ValueError(f"{name}: {msg}")
+    w = weight.detach().to(x.device if weight_on_gpu else "cpu", torch.float32).contiguous()
+    x, grad, b = (t.detach().float().contiguous() if t is not None else None for t in (x, grad, b))
+    dev = _dev(x)
+    gx = torch.empty_like(x) if "x" in need else None
+    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
+    B, Cin, N, H, W = x.shape
+
+    def call(with_x, with_w):
+        t = types.SimpleNamespace(x=_ptr(x), w=_ptr(w) if weight_on_gpu else _f32(w), grad=_ptr(grad), b=_ptr(b) if with_x else None,
+                                  gx=_ptr(gx) if with_x else None, gw=_ptr(gw) if with_w else None, B=B, Cin=Cin, N=N, H=H, W=W)
+        return fn(dev, PRECISIONS[precision], *layout(t), _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        # the C entry point's own refusals first (a call with no output launches nothing), then the gradient's shape
+        _check(call(False, False), fn.__name__)
+        if tuple(grad.shape) != want():
+            raise ValueError(f"{name}: {what[0]} {tuple(grad.shape)} is not the {what[1]} {want()}")
+        _check(call(gx is not None, gw is not None), fn.__name__)
+    return gx, gw
+
+
 def op_conv3d_backward(x, weight, grad_y, *, stride=1, pad=0, dilation=1, transposed=False, precision="bf16x3", need=("x", "w")):
     """(grad_x, grad_w) of <grad_y, conv(x, weight)> for the plain convs of the aggregation network (dffw_op_conv3d_backward: 3x3x3 and 1x3x3
     stride 1, 3x3x3 stride (1,2,2), the transposed 3x3x3; no BN, bias, ReLU or residual).  ``x`` (B,Cin,N,H,W) and ``grad_y`` float32 on the
     GPU, ``weight`` CPU/GPU float32 in PyTorch layout.  ``need``: which of "x", "w" to compute; the other entry is None.  grad_x comes from the
     adjoint conv through the forward's dispatch, grad_w from the conv_wgrad kernels; both are float32 GPU tensors."""
-    if x.device.type != "cuda" or grad_y.device.type != "cuda":
-        raise DffwError("op_conv3d_backward needs GPU tensors (no CPU fallback)")
-    if tuple(_i3(dilation)) != (1, 1, 1):
-        raise ValueError(f"op_conv3d_backward: dilation must be 1, got {dilation}")
-    if x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5:
-        raise ValueError("op_conv3d_backward: x, weight and grad_y must have 5 dimensions")
-    B, Cin, N, H, W = x.shape
-    if weight.shape[1 if not transposed else 0] != Cin:
-        raise ValueError(f"op_conv3d_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
-    Cout = weight.shape[1] if transposed else weight.shape[0]
-    k = tuple(weight.shape[2:])
-    s, p = _i3(stride), _i3(pad)
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
-    dev = _dev(x)
-    gx = torch.empty_like(x) if "x" in need else None
-    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
-
-    def call(with_x, with_w):
-        return lib.dffw_op_conv3d_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), s, p,
-                                           int(transposed), _ptr(grad_y), _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
-    with torch.cuda.device(dev):
-        # the C entry point takes grad_y's shape from the geometry: its own refusals first (a call with no output launches nothing), then the tensor
-        _check(call(False, False), "dffw_op_conv3d_backward")
-        want = conv3d_output_shape(x.shape, w.shape, stride, pad, transposed)
-        if tuple(grad_y.shape) != want:
-            raise ValueError(f"op_conv3d_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
-        _check(call(gx is not None, gw is not None), "dffw_op_conv3d_backward")
-    return gx, gw
+    checks = (lambda: tuple(_i3(dilation)) != (1, 1, 1) and f"dilation must be 1, got {dilation}",
+              lambda: (x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5) and "x, weight and grad_y must have 5 dimensions",
+              lambda: weight.shape[0 if transposed else 1] != x.shape[1] and f"weight {tuple(weight.shape)} does not take {x.shape[1]} input channels")
+    return _conv_backward(
+        lib.dffw_op_conv3d_backward, x, weight, grad_y, need, precision, checks=checks,
+        layout=lambda t: (t.x, t.B, t.Cin, t.N, t.H, t.W, t.w, weight.shape[1 if transposed else 0], _i3(weight.shape[2:]), _i3(stride), _i3(pad),
+                          int(transposed), t.grad, t.gx, t.gw),
+        want=lambda: conv3d_output_shape(x.shape, weight.shape, stride, pad, transposed), what=("grad_y", "conv's output shape"))
 
 
 def op_conv_pw_backward(x, weight, grad_y, *, pad, stride=1, dilation=1, precision="bf16x3", need=("x", "w")):
@@ -488,34 +500,13 @@ def op_conv_pw_backward(x, weight, grad_y, *, pad, stride=1, dilation=1, precisi
     (3,1,1) with pad (1,0,0) and kernel (1,1,1) with pad 0, stride 1, no bias; channels multiples of 8 up to 128.  ``x`` (B,Cin,N,H,W) and
     ``grad_y`` (B,Cout,N,H,W) float32 on the GPU, ``weight`` CPU/GPU float32 (Cout,Cin,kd,1,1); ``stride`` and ``dilation`` must be 1.  ``need``: which of "x", "w" to compute; the
     other entry is None.  grad_x comes from the adjoint conv through the forward's dispatch, grad_w from the conv_pw_wgrad kernels."""
-    if x.device.type != "cuda" or grad_y.device.type != "cuda":
-        raise DffwError("op_conv_pw_backward needs GPU tensors (no CPU fallback)")
-    if tuple(_i3(stride)) != (1, 1, 1) or tuple(_i3(dilation)) != (1, 1, 1):
-        raise ValueError(f"op_conv_pw_backward: stride and dilation must be 1, got {stride} and {dilation}")
-    if x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5:
-        raise ValueError("op_conv_pw_backward: x, weight and grad_y must have 5 dimensions")
-    B, Cin, N, H, W = x.shape
-    if weight.shape[1] != Cin:
-        raise ValueError(f"op_conv_pw_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
-    Cout = weight.shape[0]
-    k, p = tuple(weight.shape[2:]), _i3(pad)
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    x, grad_y = x.detach().float().contiguous(), grad_y.detach().float().contiguous()
-    dev = _dev(x)
-    gx = torch.empty_like(x) if "x" in need else None
-    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
-
-    def call(with_x, with_w):
-        return lib.dffw_op_conv_pw_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _f32(w), Cout, (c_int * 3)(*k), p, _ptr(grad_y),
-                                            _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
-    with torch.cuda.device(dev):
-        # the C entry point's own refusals first (a call with no output launches nothing), then grad_y's shape: the conv's output has x's volume
-        _check(call(False, False), "dffw_op_conv_pw_backward")
-        want = (B, Cout, N, H, W)
-        if tuple(grad_y.shape) != want:
-            raise ValueError(f"op_conv_pw_backward: grad_y {tuple(grad_y.shape)} is not the conv's output shape {want}")
-        _check(call(gx is not None, gw is not None), "dffw_op_conv_pw_backward")
-    return gx, gw
+    checks = (lambda: (tuple(_i3(stride)) != (1, 1, 1) or tuple(_i3(dilation)) != (1, 1, 1)) and f"stride and dilation must be 1, got {stride} and {dilation}",
+              lambda: (x.dim() != 5 or weight.dim() != 5 or grad_y.dim() != 5) and "x, weight and grad_y must have 5 dimensions",
+              lambda: weight.shape[1] != x.shape[1] and f"weight {tuple(weight.shape)} does not take {x.shape[1]} input channels")
+    return _conv_backward(
+        lib.dffw_op_conv_pw_backward, x, weight, grad_y, need, precision, checks=checks,
+        layout=lambda t: (t.x, t.B, t.Cin, t.N, t.H, t.W, t.w, weight.shape[0], _i3(weight.shape[2:]), _i3(pad), t.grad, t.gx, t.gw),
+        want=lambda: (x.shape[0], weight.shape[0]) + tuple(x.shape[2:]), what=("grad_y", "conv's output shape"))   # the conv's output has x's volume
 
 
 def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):
@@ -601,39 +592,15 @@ def op_score_conv_backward(x, weight, grad_score, *, pad, b=None, precision="bf1
     ``x`` (B,Cin,N,h,w) float32 on the GPU, ``grad_score`` (B,N,h,w) float32 on the GPU, as the loss heads write it: it stays fp32.  ``weight``
     CPU/GPU float32 (1,Cin,k,k,k).  ``b`` (B,Cin,N,h,w): a second gradient of ``x``, added into grad_x.  ``need``: which of "x", "w" to
     compute; the other entry is None.  Both come from the score_dgrad / score_wgrad kernels; grad_x is a record value of ``precision``."""
-    tensors = [x, grad_score] + ([b] if b is not None else [])
-    if any(t.device.type != "cuda" for t in tensors):
-        raise DffwError("op_score_conv_backward needs GPU tensors (no CPU fallback)")
-    if x.dim() != 5 or weight.dim() != 5:
-        raise ValueError("op_score_conv_backward: x and weight must have 5 dimensions")
-    B, Cin, N, H, W = x.shape
-    if weight.shape[0] != 1:
-        raise ValueError(f"op_score_conv_backward: weight {tuple(weight.shape)} has {weight.shape[0]} output channels, a score conv has one")
-    if weight.shape[1] != Cin:
-        raise ValueError(f"op_score_conv_backward: weight {tuple(weight.shape)} does not take {Cin} input channels")
-    if b is not None and tuple(b.shape) != tuple(x.shape):
-        raise ValueError(f"op_score_conv_backward: b {tuple(b.shape)} is not x's shape {tuple(x.shape)}")
-    if b is not None and "x" not in need:
-        raise ValueError("op_score_conv_backward: b is added to grad_x, which is not asked for")
-    k, p = tuple(weight.shape[2:]), _i3(pad)
-    w = weight.detach().to(x.device, torch.float32).contiguous()
-    x, grad_score = x.detach().float().contiguous(), grad_score.detach().float().contiguous()
-    b = b.detach().float().contiguous() if b is not None else None
-    dev = _dev(x)
-    gx = torch.empty_like(x) if "x" in need else None
-    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device) if "w" in need else None
-
-    def call(with_x, with_w):
-        return lib.dffw_op_score_conv_backward(dev, PRECISIONS[precision], _ptr(x), B, Cin, N, H, W, _ptr(w), (c_int * 3)(*k), p, _ptr(grad_score),
-                                               _ptr(b) if with_x else None, _ptr(gx) if with_x else None, _ptr(gw) if with_w else None, _stream_ptr(dev))
-    with torch.cuda.device(dev):
-        # the C entry point's own refusals first (a call with no output launches nothing), then grad_score's shape: the score volume of x
-        _check(call(False, False), "dffw_op_score_conv_backward")
-        want = (B, N, H, W)
-        if tuple(grad_score.shape) != want:
-            raise ValueError(f"op_score_conv_backward: grad_score {tuple(grad_score.shape)} is not the score volume's shape {want}")
-        _check(call(gx is not None, gw is not None), "dffw_op_score_conv_backward")
-    return gx, gw
+    checks = (lambda: (x.dim() != 5 or weight.dim() != 5) and "x and weight must have 5 dimensions",
+              lambda: weight.shape[0] != 1 and f"weight {tuple(weight.shape)} has {weight.shape[0]} output channels, a score conv has one",
+              lambda: weight.shape[1] != x.shape[1] and f"weight {tuple(weight.shape)} does not take {x.shape[1]} input channels",
+              lambda: b is not None and tuple(b.shape) != tuple(x.shape) and f"b {tuple(b.shape)} is not x's shape {tuple(x.shape)}",
+              lambda: b is not None and "x" not in need and "b is added to grad_x, which is not asked for")
+    return _conv_backward(
+        lib.dffw_op_score_conv_backward, x, weight, grad_score, need, precision, checks=checks, b=b, weight_on_gpu=True,
+        layout=lambda t: (t.x, t.B, t.Cin, t.N, t.H, t.W, t.w, _i3(weight.shape[2:]), _i3(pad), t.grad, t.b, t.gx, t.gw),
+        want=lambda: (x.shape[0],) + tuple(x.shape[2:]), what=("grad_score", "score volume's shape"))   # the score volume of x
 
 
 STEM_WEIGHT_SHAPE = (8, 3, 1, 9, 9)   # FM_measure.Focus_extraction.0.0: Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2), bias=False)

@@ -333,6 +333,14 @@ class HeadsLoss(torch.autograd.Function):
         return tuple(g * grad_out for g in ctx.saved_tensors) + (None,) * 6
 
 
+def _xw_backward(ctx, op, x, weight, grad, **kw):
+    """(grad_x, grad_w) of a conv node whose first two inputs are x and the weight: ``op`` (an engine.op_*_backward) computes those autograd
+    asks for, and the weight's gradient goes to the weight's device and dtype."""
+    need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
+    gx, gw = op(x, weight, grad, need=need, **kw)
+    return gx, gw.to(weight.device, weight.dtype) if gw is not None else None
+
+
 # ---- conv backward (DESIGN.md section 13): one plain conv of the aggregation network as an autograd node ----------------------------------------
 class Conv3d(torch.autograd.Function):
     """y = Conv3d.apply(x, weight, stride, pad, transposed, precision): the plain conv (no BN, bias or ReLU) through engine.op_conv3d, its
@@ -350,15 +358,12 @@ class Conv3d(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, weight = ctx.saved_tensors
         stride, pad, transposed, precision = ctx.geom
-        need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
         if tuple(weight.shape[2:]) in ((3, 1, 1), (1, 1, 1)):
             if transposed:
                 raise ValueError(f"conv3d backward: a transposed {tuple(weight.shape[2:])} conv is not served")
-            gx, gw = engine.op_conv_pw_backward(x, weight, grad_y, pad=pad, stride=stride, precision=precision, need=need)
+            gx, gw = _xw_backward(ctx, engine.op_conv_pw_backward, x, weight, grad_y, pad=pad, stride=stride, precision=precision)
         else:
-            gx, gw = engine.op_conv3d_backward(x, weight, grad_y, stride=stride, pad=pad, transposed=transposed, precision=precision, need=need)
-        if gw is not None:
-            gw = gw.to(weight.device, weight.dtype)
+            gx, gw = _xw_backward(ctx, engine.op_conv3d_backward, x, weight, grad_y, stride=stride, pad=pad, transposed=transposed, precision=precision)
         return gx, gw, None, None, None, None
 
 
@@ -387,11 +392,7 @@ class ScoreConv(torch.autograd.Function):
     def backward(ctx, grad_score):
         x, weight = ctx.saved_tensors
         pad, precision = ctx.geom
-        need = tuple(n for n, on in zip(("x", "w"), ctx.needs_input_grad[:2]) if on)
-        gx, gw = engine.op_score_conv_backward(x, weight, grad_score, pad=pad, precision=precision, need=need)
-        if gw is not None:
-            gw = gw.to(weight.device, weight.dtype)
-        return gx, gw, None, None
+        return _xw_backward(ctx, engine.op_score_conv_backward, x, weight, grad_score, pad=pad, precision=precision) + (None, None)
 
 
 def score_conv(x, weight, *, pad=0, precision="bf16x3"):

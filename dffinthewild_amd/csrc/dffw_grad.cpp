@@ -31,8 +31,6 @@ int dffw::check_volume(const char *family, int precision, int B, int N, int H, i
 
 namespace {
 
-bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 // What a family makes of a call's geometry and shape.  With rc set (and the error message with it) nothing else is filled in
 template <class Args>
 struct Plan {

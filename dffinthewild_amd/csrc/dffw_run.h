@@ -32,6 +32,9 @@ static constexpr auto &fail = dffw_fail;
 // `units` -- the largest count the family's kernels hold in an int, from the family's own unit size -- beyond 31 bits.  DFFW_OK, or the error set
 int check_volume(const char *family, int precision, int B, int N, int H, int W, std::initializer_list<int> channels, int div, int64_t units, const char *unit);
 
+// is p a multiple of n (a power of two)?  A null pointer is
+inline bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \

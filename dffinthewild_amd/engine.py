@@ -11,6 +11,7 @@ import threading
 import types
 from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int64, c_void_p
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,6 +38,14 @@ class _Tap(ctypes.Structure):
 class _Prof(ctypes.Structure):
     _fields_ = [("kernel", c_char_p), ("layer", c_char_p), ("flops", ctypes.c_double), ("bytes", ctypes.c_double),
                 ("ms", c_float)]
+
+
+class AdamTensor(ctypes.Structure):
+    """dffw_adam_tensor: one entry of dffw_adam_step's list."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", c_int64)]
+
+
+assert ctypes.sizeof(AdamTensor) == 40   # op_adam_step builds the table as an (n, 5) array of 8-byte words
 
 
 class SimParams(ctypes.Structure):
@@ -158,10 +167,13 @@ def _load():
     lib.dffw_score_conv_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_score_conv_wgrad.argtypes = [c_int, c_int, c_void_p, c_void_p] + [c_int] * 5 + [POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_op_score_conv_backward.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, POINTER(c_int), POINTER(c_int)] + [c_void_p] * 5
+    lib.dffw_adam_tensors_per_launch.argtypes = []
+    lib.dffw_adam_step.argtypes = [c_int, POINTER(AdamTensor), c_int, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]
     return lib
 
 
 lib = _load()
+ADAM_TENSORS_PER_LAUNCH = lib.dffw_adam_tensors_per_launch()   # tensors one launch of dffw_adam_step takes; a longer list takes several launches
 COMM_ID_BYTES = 128
 RAW_NORM_F64 = 16   # DFFW_RAW_NORM_F64: the FS6 loader's float64 normalisation
 AUG_NPARAMS = 8     # DFFW_AUG_NPARAMS: crop row, crop col, contrast, brightness, gamma, flip_x, flip_y, angle
@@ -185,6 +197,7 @@ ABI_SYMBOLS = (
     "dffw_pool_backward", "dffw_pool3_backward", "dffw_op_pool_backward", "dffw_op_pool3_backward",
     "dffw_stem_wgrad_workspace_bytes", "dffw_stem_wgrad", "dffw_op_stem_backward",
     "dffw_score_conv_dgrad", "dffw_score_conv_wgrad_workspace_bytes", "dffw_score_conv_wgrad", "dffw_op_score_conv_backward",
+    "dffw_adam_tensors_per_launch", "dffw_adam_step",
 )
 
 
@@ -693,6 +706,51 @@ def op_bn_train_backward(x, y, grad_y, gamma, save_mean, save_invstd, *, relu=Fa
         _check(lib.dffw_op_bn_train_backward(dev, PRECISIONS[precision], _ptr(x), _ptr(y), _ptr(grad_y), B, C, N, H, W, _ptr(g), _ptr(mean), _ptr(invstd),
                                              int(bool(relu)), _ptr(gx), _ptr(gres), _ptr(gg), _ptr(gb), _stream_ptr(dev)), "dffw_op_bn_train_backward")
     return gx, gres, gg, gb
+
+
+def op_adam_step(params, grads, exp_avgs, exp_avg_sqs, *, step, lr, betas=(0.9, 0.99), eps=1e-8):
+    """One Adam step over a whole parameter list in ceil(n / ADAM_TENSORS_PER_LAUNCH) launches (dffw_adam_step): four lists of
+    float32 contiguous tensors on ONE GPU, the same shapes position by position.  ``params``, ``exp_avgs`` and ``exp_avg_sqs`` are updated in
+    place, ``grads`` are only read; ``step`` is the step count after the increment (1 for the first step).  torch.optim.Adam's arithmetic
+    without weight decay, amsgrad or maximize; the betas default to the reference training scripts' (0.9, 0.99).  Enqueue-only on the current
+    stream of that GPU: nothing is allocated, copied or waited for."""
+    lists = (list(params), list(grads), list(exp_avgs), list(exp_avg_sqs))
+    n = len(lists[0])
+    if any(len(l) != n for l in lists):
+        raise ValueError(f"op_adam_step: the four lists hold {[len(l) for l in lists]} tensors")
+    f32, T = torch.float32, torch.Tensor
+    try:   # whole lists at a time (a step over 200 tensors is bound by this Python); the loop below finds the offender and words the refusal
+        shapes = [t.shape for t in lists[0]]
+        good = all({t.dtype for t in l} <= {f32} and all(map(T.is_contiguous, l)) and [t.shape for t in l] == shapes for l in lists)
+    except (AttributeError, TypeError):
+        good = False
+    if not good:
+        for what, l in zip(("params", "grads", "exp_avgs", "exp_avg_sqs"), lists):
+            for i, t in enumerate(l):
+                if not isinstance(t, torch.Tensor) or t.dtype != f32:
+                    raise ValueError(f"op_adam_step: {what}[{i}] is not a float32 tensor")
+                if not t.is_contiguous():
+                    raise ValueError(f"op_adam_step: {what}[{i}] is not contiguous")
+                if t.shape != lists[0][i].shape:
+                    raise ValueError(f"op_adam_step: {what}[{i}] {tuple(t.shape)} does not have the shape of params[{i}] {tuple(lists[0][i].shape)}")
+    devs = set().union(*(map(T.get_device, l) for l in lists))   # -1: a CPU tensor
+    if -1 in devs:
+        raise DffwError("op_adam_step needs GPU tensors (no CPU fallback)")
+    if len(devs) > 1:
+        raise ValueError("op_adam_step: the tensors are on more than one GPU (one call per device)")
+    b1, b2 = betas
+    # dffw_adam_tensor is five 8-byte words: the table is an (n, 5) int64 array
+    table = np.empty((n, 5), dtype=np.uint64)
+    for k, l in enumerate(lists):
+        table[:, k] = np.fromiter(map(T.data_ptr, l), dtype=np.uint64, count=n)
+    table[:, 4] = np.fromiter(map(T.numel, lists[0]), dtype=np.uint64, count=n)
+    tp = table.ctypes.data_as(POINTER(AdamTensor))
+    if not n:   # the library's refusal of an empty list, without a device to name
+        _check(lib.dffw_adam_step(0, tp, 0, int(step), float(lr), float(b1), float(b2), float(eps), None), "dffw_adam_step")
+        return
+    dev = devs.pop()
+    with torch.cuda.device(dev):
+        _check(lib.dffw_adam_step(dev, tp, n, int(step), float(lr), float(b1), float(b2), float(eps), _stream_ptr(dev)), "dffw_adam_step")
 
 
 def probe_peaks(device=0):

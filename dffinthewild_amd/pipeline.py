@@ -543,3 +543,89 @@ def avg_pool_pyramid(x, *, precision="bf16x3"):
     """(p2, p4, p8): the average pools (1,2,2), (1,4,4), (1,8,8) that hourglassup takes of one volume x (B,C,N,H,W), H and W multiples of 8,
     with the gradient of x from one kernel launch."""
     return AvgPoolPyramid.apply(x, precision)
+
+
+# ---- the optimiser (DESIGN.md section 20): the reference's torch.optim.Adam(lr, betas=(0.9, 0.99)) on one multi-tensor HIP kernel ----------------
+class Adam(torch.optim.Optimizer):
+    """optimizer = Adam(model.parameters(), lr, betas=(0.9, 0.99), eps=1e-8); loss.backward(); optimizer.step(): what the reference's training
+    scripts do, with every parameter of a group and device updated by ONE engine.op_adam_step call (ceil(n / engine.ADAM_TENSORS_PER_LAUNCH)
+    launches, enqueue-only).  Parameters are float32 contiguous CUDA tensors.  The per-parameter state has torch.optim.Adam's keys and types
+    (capturable=False): ``step`` a float32 CPU scalar, ``exp_avg`` and ``exp_avg_sq`` zeros_like(param); the groups carry its options.  A
+    state_dict therefore loads into torch.optim.Adam and back.  weight_decay, amsgrad and maximize are not built: a value that asks for one is
+    refused, here and when a loaded checkpoint brings it."""
+
+    _NOT_BUILT = (("weight_decay", 0), ("amsgrad", False), ("maximize", False))
+
+    def __init__(self, params, lr, betas=(0.9, 0.99), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Adam: invalid learning rate {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Adam: invalid eps {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Adam: invalid betas {betas}")
+        # the option keys of torch.optim.Adam's groups, so that a checkpoint of one class loads into the other
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
+                        differentiable=False, fused=None, decoupled_weight_decay=False)
+        self._refuse_not_built(defaults)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            self._refuse_not_built(group)
+
+    @classmethod
+    def _refuse_not_built(cls, group):
+        for name, off in cls._NOT_BUILT:
+            if group.get(name, off) != off:
+                raise ValueError(f"Adam: {name}={group[name]!r} is not built (DESIGN.md section 20: plain Adam only)")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError("Adam.step: closures are not supported")
+        for gi, group in enumerate(self.param_groups):
+            self._refuse_not_built(group)
+            rows = []   # (p, grad, exp_avg, exp_avg_sq, step) of every parameter that has a gradient
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.is_sparse:
+                    raise ValueError("Adam: sparse gradients are not supported")
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                rows.append((p, g if g.is_contiguous() else g.contiguous(), state["exp_avg"], state["exp_avg_sq"], state["step"]))
+            if not rows:
+                continue
+            counts, bump = self._step_counts(gi, rows)
+            # one call per device -- and per step count, which differs inside a group only after a partial load
+            devs = [r[0].device for r in rows]
+            if counts.count(counts[0]) == len(counts) and devs.count(devs[0]) == len(devs):
+                calls = {(devs[0], int(counts[0]) + 1): rows}
+            else:
+                calls = {}
+                for r, d, t in zip(rows, devs, counts):
+                    calls.setdefault((d, int(t) + 1), []).append(r)
+            for (_, t), rs in calls.items():
+                ps, gs, ms, vs, _ = zip(*rs)
+                engine.op_adam_step(ps, gs, ms, vs, step=t, lr=group["lr"], betas=group["betas"], eps=group["eps"])
+            bump()   # counted once the updates are enqueued: a refused call leaves the counts as they were
+        return None
+
+    def _step_counts(self, gi, rows):
+        """(the step counts of ``rows``' parameters before this step, a callable that adds 1 to each).  The ``step`` tensors of the parameters
+        that step together are kept as the elements of ONE float32 CPU vector -- each state["step"] a 0-dim view of it, so that nothing changes
+        for a reader of the state -- which is read and incremented whole: 200 separate CPU scalars cost more host time than the update's
+        launches.  Whatever replaced the views since (load_state_dict, a first step) is packed again here."""
+        steps = [r[4] for r in rows]
+        cache = self.__dict__.setdefault("_packed_steps", {})   # per param group
+        packed = cache.get(gi)
+        if packed is None or len(packed[1]) != len(steps) or any(a is not b for a, b in zip(packed[1], steps)):
+            base = torch.stack([s.detach().to("cpu", torch.float32).reshape(()) for s in steps])
+            views = list(base.unbind(0))
+            for r, v in zip(rows, views):
+                self.state[r[0]]["step"] = v
+            packed = cache[gi] = (base, views)
+        return packed[0].tolist(), lambda: packed[0].add_(1)
+

@@ -505,6 +505,33 @@ int dffw_op_score_conv_backward(int device, int precision, const float *x, int B
                                 const int kernel[3], const int pad[3], const float *grad_score, const float *b, float *grad_x, float *grad_w,
                                 void *hip_stream);
 
+/* ---- the Adam step -----------------------------------------------------------------------------------------------------------
+ * What the reference's training scripts do after backward(): torch.optim.Adam(lr, betas=(0.9, 0.99)) without weight decay, amsgrad or gradient
+ * scaling, for the WHOLE parameter list in a handful of launches of dffw::adam_kernel.  With t = step, the count after the increment (t >= 1):
+ *     m' = beta1 m + (1 - beta1) g          v' = beta2 v + (1 - beta2) g^2
+ *     d  = sqrt(v') / sqrt(1 - beta2^t) + eps          p' = p - (lr / (1 - beta1^t)) m' / d
+ * The scalars are computed on the host in double and rounded once to fp32, as torch's single-tensor path has them; every element operation is
+ * one fp32 rounding (correctly rounded sqrt and division, no fma contraction).  param, exp_avg and exp_avg_sq are updated in place, grad is only
+ * read; NaN and Inf propagate and no step is skipped.  All pointers are device fp32, 4-byte aligned, of numel elements; a tensor whose four
+ * pointers are 16-byte aligned moves in 16-byte accesses, any other element by element, with the same bits either way.
+ * The list travels as the kernel's argument, at most dffw_adam_tensors_per_launch() tensors (and 2^34 elements) per launch; a longer list takes
+ * several launches on hip_stream.  Enqueue-only: no device allocation, no copy, no synchronisation, no atomics.  A tensor's result does not depend
+ * on its place in the list, the launch it lands in or the grid: passed alone it gives identical bits.  Tensors must not overlap.
+ * DFFW_EINVAL before any launch and before the GPU is touched: tensors NULL or n_tensors < 1; numel < 0 or >= 2^31; a NULL pointer in an entry
+ * with numel > 0; a pointer that is not 4-byte aligned; step < 1; lr, eps or a beta that is not finite; lr < 0, eps < 0, a beta outside [0, 1).
+ * An entry with numel == 0 is skipped; a list of such entries only is DFFW_OK without a launch.  dffw_last_op_kernels names the kernel once per
+ * launch. */
+typedef struct dffw_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t numel;
+} dffw_adam_tensor;
+int dffw_adam_tensors_per_launch(void);
+int dffw_adam_step(int device, const dffw_adam_tensor *tensors, int n_tensors, int64_t step, double lr, double beta1, double beta2, double eps,
+                   void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

@@ -1,5 +1,6 @@
 // Backward of the convs: the C ABI of the four weight-gradient kernel families.
 //   plain    3x3x3 / 1x3x3 stride 1, 3x3x3 stride (1,2,2), transposed 3x3x3   DESIGN.md §13   dffw_conv_wgrad.hip
+//   cat      3x3x3 stride 1 over the concatenation of two sources             DESIGN.md §21   dffw_conv_wgrad.hip (the plain body, two-source fill)
 //   pw       3x1x1 pad (1,0,0) and 1x1x1: no in-plane taps                    DESIGN.md §15   dffw_conv_pw_wgrad.hip
 //   stem     Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2))             DESIGN.md §17   dffw_stem_wgrad.hip
 //   score    Cin -> 1, 1x1x1 and 3x3x3 (and their data gradient)              DESIGN.md §19   dffw_score_grad.hip
@@ -107,6 +108,42 @@ Plan<WgradArgs> plan_conv(int precision, const void *x, int B, int Cin, int N, i
     a.flush_units = std::min(sw.wgrad_flush_units, wgrad::FLUSH_UNITS);
     p.grid_x = conv_wgrad_grid_x(a, sw.wgrad_wgs);
     p.bytes = (int64_t)p.grid_x * a.kd * a.ncot * a.ncig * wgrad::BLOCK * (int64_t)sizeof(double);
+    return p;
+}
+
+// ---- cat: the 3x3x3 stride-1 pad-1 conv whose input is the concatenation of xa (Ca channels) and xb (Cb channels) ---------------------------------
+// The geometry is the entry point's name; the shape's refusals are check_volume's (Cout as a plain conv's) and then this family's own rule for
+// the two sources, whose sum may pass 128: that is what the forward's two-source fill is known to serve
+Plan<WgradCatArgs> plan_conv_cat(int precision, const void *xa, int Ca, const void *xb, int Cb, int B, int N, int H, int W, const void *gy, int Cout) {
+    Plan<WgradCatArgs> p{};
+    const int64_t units = (int64_t)B * N * ((H + wgrad::TY - 1) / wgrad::TY) * ((W + wgrad::TX - 1) / wgrad::TX);
+    p.rc = check_volume("conv backward over a concatenation", precision, B, N, H, W, {Cout}, 1, units, "units");
+    if (p.rc) return p;
+    for (int c : {Ca, Cb})
+        if (c < 8 || c % 8 || c > 128 || Ca + Cb > 192) {
+            p.rc = fail(DFFW_EINVAL, "conv backward over a concatenation needs Ca and Cb multiples of 8 from 8 to 128 with Ca + Cb <= 192, got Ca=%d Cb=%d", Ca, Cb);
+            return p;
+        }
+    const Switches sw = Switches::read();
+    WgradCatArgs &a = p.a;
+    a.g = (const uint16_t *)gy;
+    a.f_a = (const uint16_t *)xa;
+    a.f_b = (const uint16_t *)xb;
+    a.B = B;
+    a.N = N;
+    a.Hg = H;
+    a.Wg = W;
+    a.Cg = Cout;
+    a.Ca = Ca;
+    a.Cb = Cb;
+    a.tiles_y = (H + wgrad::TY - 1) / wgrad::TY;
+    a.tiles_x = (W + wgrad::TX - 1) / wgrad::TX;
+    a.total_tiles = B * N * a.tiles_y * a.tiles_x;
+    a.ncot = (Cout + wgrad::CO_T - 1) / wgrad::CO_T;
+    a.ncig = (Ca + Cb + wgrad::CI_G - 1) / wgrad::CI_G;
+    a.flush_units = std::min(sw.wgrad_flush_units, wgrad::FLUSH_UNITS);
+    p.grid_x = conv_wgrad_cat_grid_x(a, sw.wgrad_wgs);
+    p.bytes = (int64_t)p.grid_x * 3 * a.ncot * a.ncig * wgrad::BLOCK * (int64_t)sizeof(double);
     return p;
 }
 
@@ -218,6 +255,9 @@ int dffw::conv_backward_check(int precision, int B, int Cin, int N, int H, int W
                               int transposed) {
     return plan_conv(precision, nullptr, B, Cin, N, H, W, nullptr, Cout, kernel, stride, pad, transposed).rc;
 }
+int dffw::conv_cat_backward_check(int precision, int B, int Ca, int Cb, int N, int H, int W, int Cout) {
+    return plan_conv_cat(precision, nullptr, Ca, nullptr, Cb, B, N, H, W, nullptr, Cout).rc;
+}
 int dffw::conv_pw_backward_check(int precision, int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int pad[3]) {
     return plan_pw(precision, nullptr, B, Cin, N, H, W, nullptr, Cout, kernel, pad).rc;
 }
@@ -243,6 +283,22 @@ int dffw_conv_wgrad(int device, int precision, const void *x, int B, int Cin, in
     p.a.partial = (double *)workspace;
     return launch_record("wgrad", p.bytes, workspace_bytes, device, conv_wgrad_kernel_name(precision, p.sub), "dffw::conv_wgrad_finish_kernel",
                          [&] { return launch_conv_wgrad(precision, p.sub, p.a, p.grid_x, grad_w, (hipStream_t)hip_stream); });
+}
+
+int64_t dffw_conv_cat_wgrad_workspace_bytes(int B, int Ca, int Cb, int N, int H, int W, int Cout) {
+    return plan_conv_cat(0, nullptr, Ca, nullptr, Cb, B, N, H, W, nullptr, Cout).bytes;
+}
+
+int dffw_conv_cat_wgrad(int device, int precision, const void *xa, int Ca, const void *xb, int Cb, int B, int N, int H, int W, const void *grad_y, int Cout,
+                        float *grad_w, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    Plan<WgradCatArgs> p = plan_conv_cat(precision, xa, Ca, xb, Cb, B, N, H, W, grad_y, Cout);
+    if (p.rc) return p.rc;
+    if (!xa || !xb || !grad_y || !grad_w || !workspace) return fail(DFFW_EINVAL, "null argument");
+    if (!aligned(xa, 16) || !aligned(xb, 16) || !aligned(grad_y, 16) || !aligned(workspace, 8)) return fail(DFFW_EINVAL, "records must be 16-byte aligned");
+    p.a.partial = (double *)workspace;
+    return launch_record("wgrad", p.bytes, workspace_bytes, device, conv_wgrad_cat_kernel_name(precision), "dffw::conv_wgrad_finish_kernel",
+                         [&] { return launch_conv_wgrad_cat(precision, p.a, p.grid_x, grad_w, (hipStream_t)hip_stream); });
 }
 
 int64_t dffw_conv_pw_wgrad_workspace_bytes(int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int pad[3]) {

@@ -116,6 +116,17 @@ int run_wgrad_op(int device, int precision, int B, int N, Staged x, Staged gy, i
         if (real(r)) r.err = call(xa.p, ya.p, ws, r.s);
     });
 }
+// ... of a conv with two sources: `call(xa's records, xb's records, grad_y's records, workspace, stream)`
+int run_wgrad_op(int device, int precision, int B, int N, Staged xa, Staged xb, Staged gy, int64_t wsb, hipStream_t s,
+                 const std::function<int(const void *, const void *, const void *, void *, hipStream_t)> &call) {
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, s, false, [&](Run &r) {
+        Act aa = stage_in(r, xa.t, B, xa.C, N, xa.H, xa.W), ba = stage_in(r, xb.t, B, xb.C, N, xb.H, xb.W), ya = stage_in(r, gy.t, B, gy.C, N, gy.H, gy.W);
+        void *ws = r.raw(wsb);
+        if (real(r)) r.err = call(aa.p, ba.p, ya.p, ws, r.s);
+    });
+}
 
 }  // namespace
 
@@ -418,6 +429,52 @@ int dffw_op_conv3d_backward(int device, int precision, const float *x, int B, in
     return run_wgrad_op(device, precision, B, N, {x, Cin, H, W}, {grad_y, Cout, Ho, Wo}, wsb, (hipStream_t)hip_stream,
                         [&](const void *xr, const void *yr, void *ws, hipStream_t s) {
                             return dffw_conv_wgrad(device, precision, xr, B, Cin, N, H, W, yr, Cout, kernel, stride, pad, transposed, grad_w, ws, wsb, s);
+                        });
+}
+
+// ---- the 3x3x3 stride-1 conv over the concatenation of xa and xb: weight (Cout, Ca + Cb, 3,3,3) host fp32
+int dffw_op_conv_cat_backward(int device, int precision, const float *xa, int Ca, const float *xb, int Cb, int B, int N, int H, int W, const float *weight,
+                              int Cout, const float *grad_y, float *grad_xa, float *grad_xb, float *grad_w, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (int rc = conv_cat_backward_check(precision, B, Ca, Cb, N, H, W, Cout)) return rc;
+    if (!xa || !xb || !grad_y || ((grad_xa || grad_xb) && !weight)) return fail(DFFW_EINVAL, "null argument");
+    const int k3[3] = {3, 3, 3}, one[3] = {1, 1, 1};
+    const int64_t taps = 27, plane = (int64_t)N * H * W;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // grad_xa, grad_xb: the adjoint conv over grad_y (filter flipped, in / out channels swapped), through dffw_op_conv3d like every plain conv's.
+    // The forward's dispatch picks its kernel, and with it the order of the fp32 sums, by the number of output channels too, so two convs of Ca
+    // and Cb output channels need not give the bits of one of Ca + Cb.  Where that one exists (Ca + Cb <= 128) it is run, once, and its output
+    // split: the halves of dffw_op_conv3d_backward's grad_x, bit for bit.  Beyond 128 channels no single conv is served: one per source, on the
+    // weight's channels [0, Ca) and [Ca, Ca + Cb), each of at most 128 output channels
+    const struct { float *out; int c0, C; } halves[2] = {{grad_xa, 0, Ca}, {grad_xb, Ca, Cb}};
+    if ((grad_xa || grad_xb) && Ca + Cb <= 128) {
+        HIPCHK(hipSetDevice(device));
+        OpBlock gx(s);
+        HIPCHK(gx.alloc(B * (Ca + Cb) * plane * (int64_t)sizeof(float)));
+        if (int rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, H, W, adjoint_filter(weight, Cout, Ca + Cb, taps).data(), Ca + Cb, k3, one, one, one, 0,
+                                    nullptr, nullptr, nullptr, 0, (float *)gx.p, hip_stream))
+            return rc;
+        for (const auto &h : halves)   // (B, Ca + Cb, N, H, W) -> (B, C, N, H, W): one row of C * plane floats per sample
+            if (h.out)
+                HIPCHK(hipMemcpy2DAsync(h.out, h.C * plane * sizeof(float), (const float *)gx.p + h.c0 * plane, (Ca + Cb) * plane * sizeof(float),
+                                        h.C * plane * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    } else {
+        for (const auto &h : halves) {
+            if (!h.out) continue;
+            std::vector<float> ws((size_t)Cout * h.C * taps);   // weight[:, c0 : c0 + C]
+            for (int co = 0; co < Cout; ++co)
+                std::copy(weight + ((size_t)co * (Ca + Cb) + h.c0) * taps, weight + ((size_t)co * (Ca + Cb) + h.c0 + h.C) * taps, ws.begin() + (size_t)co * h.C * taps);
+            if (int rc = dffw_op_conv3d(device, precision, grad_y, B, Cout, N, H, W, adjoint_filter(ws.data(), Cout, h.C, taps).data(), h.C, k3, one, one, one, 0,
+                                        nullptr, nullptr, nullptr, 0, h.out, hip_stream))
+                return rc;
+        }
+    }
+    if (!grad_w) return DFFW_OK;
+    const int64_t wsb = dffw_conv_cat_wgrad_workspace_bytes(B, Ca, Cb, N, H, W, Cout);
+    return run_wgrad_op(device, precision, B, N, {xa, Ca, H, W}, {xb, Cb, H, W}, {grad_y, Cout, H, W}, wsb, s,
+                        [&](const void *ar, const void *br, const void *yr, void *ws, hipStream_t s) {
+                            return dffw_conv_cat_wgrad(device, precision, ar, Ca, br, Cb, B, N, H, W, yr, Cout, grad_w, ws, wsb, s);
                         });
 }
 

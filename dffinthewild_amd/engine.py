@@ -137,6 +137,10 @@ def _load():
     lib.dffw_conv_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_conv_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_conv_cat_wgrad_workspace_bytes.argtypes = [c_int] * 7
+    lib.dffw_conv_cat_wgrad_workspace_bytes.restype = c_int64
+    lib.dffw_conv_cat_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_op_conv_cat_backward.argtypes = [c_int, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [POINTER(c_float), c_int] + [c_void_p] * 5
     c_double = ctypes.c_double
     lib.dffw_bn_train_workspace_bytes.argtypes = [c_int] * 5
     lib.dffw_bn_train_workspace_bytes.restype = c_int64
@@ -198,6 +202,7 @@ ABI_SYMBOLS = (
     "dffw_stem_wgrad_workspace_bytes", "dffw_stem_wgrad", "dffw_op_stem_backward",
     "dffw_score_conv_dgrad", "dffw_score_conv_wgrad_workspace_bytes", "dffw_score_conv_wgrad", "dffw_op_score_conv_backward",
     "dffw_adam_tensors_per_launch", "dffw_adam_step",
+    "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward",
 )
 
 
@@ -520,6 +525,45 @@ def op_conv_pw_backward(x, weight, grad_y, *, pad, stride=1, dilation=1, precisi
         lib.dffw_op_conv_pw_backward, x, weight, grad_y, need, precision, checks=checks,
         layout=lambda t: (t.x, t.B, t.Cin, t.N, t.H, t.W, t.w, weight.shape[0], _i3(weight.shape[2:]), _i3(pad), t.grad, t.gx, t.gw),
         want=lambda: (x.shape[0], weight.shape[0]) + tuple(x.shape[2:]), what=("grad_y", "conv's output shape"))   # the conv's output has x's volume
+
+
+def op_conv_cat_backward(xa, xb, weight, grad_y, *, precision="bf16x3", need=("xa", "xb", "w")):
+    """(grad_xa, grad_xb, grad_w) of <grad_y, conv(cat([xa, xb], 1), weight)> for the convs whose input is a channel concatenation
+    (dffw_op_conv_cat_backward): kernel (3,3,3), stride 1, pad 1, no bias; ``xa`` (B,Ca,N,H,W), ``xb`` (B,Cb,N,H,W) and
+    ``grad_y`` (B,Cout,N,H,W) float32 on the GPU, ``weight`` CPU/GPU float32 (Cout,Ca+Cb,3,3,3); Ca, Cb, Cout multiples of 8 from 8 to 128,
+    Ca + Cb <= 192.  ``need``: which of "xa", "xb", "w" to compute; the other entries are None.  grad_xa / grad_xb are two adjoint convs on the
+    weight's slices through the forward's dispatch, grad_w comes from the conv_wgrad_cat kernels; the concatenation is never built."""
+    name = "op_conv_cat_backward"
+    # the shapes first (they need no GPU), then the device; the channel counts' limits are the library's to refuse
+    checks = (lambda: any(t.dim() != 5 for t in (xa, xb, weight, grad_y)) and "xa, xb, weight and grad_y must have 5 dimensions",
+              lambda: (xa.shape[0], *xa.shape[2:]) != (xb.shape[0], *xb.shape[2:]) and
+              f"xa {tuple(xa.shape)} and xb {tuple(xb.shape)} differ outside the channel axis",
+              lambda: tuple(weight.shape[2:]) != (3, 3, 3) and f"the conv over a concatenation is 3x3x3 stride 1 pad 1, got a {tuple(weight.shape[2:])} kernel",
+              lambda: weight.shape[1] != xa.shape[1] + xb.shape[1] and
+              f"weight {tuple(weight.shape)} does not take {xa.shape[1]} + {xb.shape[1]} input channels",
+              lambda: tuple(grad_y.shape) != (xa.shape[0], weight.shape[0], *xa.shape[2:]) and
+              f"grad_y {tuple(grad_y.shape)} is not the conv's output shape {(xa.shape[0], weight.shape[0], *xa.shape[2:])}",
+              lambda: set(need) - {"xa", "xb", "w"} and f"need {tuple(need)} names something other than 'xa', 'xb', 'w'")
+    for check in checks:
+        msg = check()
+        if msg:
+            raise ValueError(f"{name}: {msg}")
+    if any(t.device.type != "cuda" for t in (xa, xb, grad_y)):
+        raise DffwError(f"{name} needs GPU tensors (no CPU fallback)")
+    if len({t.device for t in (xa, xb, grad_y)}) != 1:
+        raise ValueError(f"{name}: xa, xb and grad_y must be on one GPU")
+    w = weight.detach().to("cpu", torch.float32).contiguous()
+    xa, xb, grad_y = (t.detach().float().contiguous() for t in (xa, xb, grad_y))
+    dev = _dev(xa)
+    B, Ca, N, H, W = xa.shape
+    Cb, Cout = xb.shape[1], w.shape[0]
+    gxa = torch.empty_like(xa) if "xa" in need else None
+    gxb = torch.empty_like(xb) if "xb" in need else None
+    gw = torch.empty(tuple(w.shape), dtype=torch.float32, device=xa.device) if "w" in need else None
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_conv_cat_backward(dev, PRECISIONS[precision], _ptr(xa), Ca, _ptr(xb), Cb, B, N, H, W, _f32(w), Cout, _ptr(grad_y), _ptr(gxa),
+                                             _ptr(gxb), _ptr(gw), _stream_ptr(dev)), "dffw_op_conv_cat_backward")
+    return gxa, gxb, gw
 
 
 def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):

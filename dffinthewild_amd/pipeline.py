@@ -375,6 +375,43 @@ def conv3d(x, weight, *, stride=1, pad=0, transposed=False, precision="bf16x3"):
     return Conv3d.apply(x, weight, stride, pad, transposed, precision)
 
 
+# ---- a conv over a channel concatenation: dres2/3/4.conv0, SPP_module.combine1 / combine2 --------------------------------
+class ConvCat3d(torch.autograd.Function):
+    """y = ConvCat3d.apply(xa, xb, weight, precision): the 3x3x3 stride-1 pad-1 conv of cat([xa, xb], 1) through engine.op_conv3d; its backward
+    through engine.op_conv_cat_backward, which reads the two tensors as they are: two adjoint convs for xa and xb, the conv_wgrad_cat kernels
+    for the weight (up to 128 + 64 = 192 input channels, which Conv3d's backward refuses)."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, weight, precision="bf16x3"):
+        _dev(xa, "xa")
+        _dev(xb, "xb")
+        ctx.save_for_backward(xa, xb, weight)
+        ctx.precision = precision
+        return engine.op_conv3d(torch.cat([xa.detach().float(), xb.detach().float()], 1), weight, stride=1, pad=1, precision=precision)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        xa, xb, weight = ctx.saved_tensors
+        need = tuple(n for n, on in zip(("xa", "xb", "w"), ctx.needs_input_grad[:3]) if on)
+        gxa, gxb, gw = engine.op_conv_cat_backward(xa, xb, weight, grad_y, precision=ctx.precision, need=need)
+        return gxa, gxb, gw.to(weight.device, weight.dtype) if gw is not None else None, None
+
+
+def conv3d_cat(xa, xb, weight, *, precision="bf16x3"):
+    """conv(cat([xa, xb], 1), weight) on the HIP kernels with gradients for all three: xa (B,Ca,N,H,W) and xb (B,Cb,N,H,W) float32 CUDA, weight
+    (Cout,Ca+Cb,3,3,3) in PyTorch layout (CPU or CUDA); stride 1, pad 1, no bias.  Ca, Cb and Cout multiples of 8 from 8 to 128, Ca + Cb <= 192:
+    the hourglasses' conv0 and the pyramid's combine1 / combine2.  The forward is bit for bit conv3d on the concatenation."""
+    if xa.dim() != 5 or xb.dim() != 5 or weight.dim() != 5:
+        raise ValueError("conv3d_cat: xa, xb and weight must have 5 dimensions")
+    if (xa.shape[0], *xa.shape[2:]) != (xb.shape[0], *xb.shape[2:]):
+        raise ValueError(f"conv3d_cat: xa {tuple(xa.shape)} and xb {tuple(xb.shape)} differ outside the channel axis")
+    if tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"conv3d_cat: the conv over a concatenation is 3x3x3 stride 1 pad 1, got a {tuple(weight.shape[2:])} kernel")
+    if weight.shape[1] != xa.shape[1] + xb.shape[1]:
+        raise ValueError(f"conv3d_cat: weight {tuple(weight.shape)} does not take {xa.shape[1]} + {xb.shape[1]} input channels")
+    return ConvCat3d.apply(xa, xb, weight, precision)
+
+
 # ---- the score convs (DESIGN.md section 19): Cin -> 1, the convs whose outputs the loss heads read --------------------------------------------
 class ScoreConv(torch.autograd.Function):
     """s = ScoreConv.apply(x, weight, pad, precision): a conv with ONE output channel (classif1.0 / classif2.0 / classif3.0: 1x1x1;

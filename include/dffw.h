@@ -532,6 +532,29 @@ int dffw_adam_tensors_per_launch(void);
 int dffw_adam_step(int device, const dffw_adam_tensor *tensors, int n_tensors, int64_t step, double lr, double beta1, double beta2, double eps,
                    void *hip_stream);
 
+/* ---- backward of a conv over a channel concatenation ------------------------------------------------------------------------
+ * The five convs of the aggregation network whose input is torch.cat([xa, xb], 1): dres2/3/4.conv0, SPP_module.combine1 and combine2.  One
+ * geometry, so it is no argument: kernel (3,3,3), stride 1, pad (1,1,1), not transposed, no bias.  xa (Ca channels) and xb (Cb channels) share
+ * one volume (B,N,H,W); Ca, Cb and Cout multiples of 8 from 8 to 128, Ca + Cb <= 192.  The concatenation is never materialised.
+ *   grad_w   (Cout, Ca + Cb, 3,3,3) device fp32 = d<grad_y, conv(cat(xa, xb), weight)>/dweight by dffw::conv_wgrad_cat_kernel +
+ *            dffw::conv_wgrad_finish_kernel (dffw_last_op_kernels lists them): the arithmetic of dffw_conv_wgrad, the footprint read from the
+ *            two record tensors; where Ca + Cb <= 128 the bits are those of dffw_conv_wgrad on the concatenated records.
+ *   grad_xa, grad_xb   two adjoint convs through the forward's own dispatch, on the weight's channels [0, Ca) and [Ca, Ca + Cb): each carries
+ *            the bits a single adjoint conv would give that half.  A skip tensor's other gradient is added by dffw_grad_combine.
+ * dffw_conv_cat_wgrad: enqueue-only on activation RECORDS (16-byte aligned), no allocation; workspace:
+ * dffw_conv_cat_wgrad_workspace_bytes(...) bytes, 8-byte aligned, need not be cleared (0 for refused arguments; too short: DFFW_ENOMEM); for
+ * Ca + Cb <= 128 it is dffw_conv_wgrad_workspace_bytes of the concatenation.  DFFW_EINVAL before any launch and before the GPU is touched, in
+ * this order: an unknown precision; B, N, H or W below 1; Cout out of range; 2^31 units of 4 x 16 pixels and more; Ca or Cb out of range or
+ * Ca + Cb > 192 (the message names both); a null pointer; a misaligned one.
+ * dffw_op_conv_cat_backward: xa (B,Ca,N,H,W), xb (B,Cb,N,H,W), grad_y (B,Cout,N,H,W) device fp32; weight host fp32 (Cout, Ca + Cb, 3,3,3) (may
+ * be NULL without grad_xa and grad_xb); grad_xa, grad_xb, grad_w device fp32 or NULL (with all three NULL nothing is launched and only the
+ * refusals are returned); allocates, poisons its workspace with 0xFF and synchronises. */
+int64_t dffw_conv_cat_wgrad_workspace_bytes(int B, int Ca, int Cb, int N, int H, int W, int Cout);
+int dffw_conv_cat_wgrad(int device, int precision, const void *xa, int Ca, const void *xb, int Cb, int B, int N, int H, int W, const void *grad_y,
+                        int Cout, float *grad_w, void *workspace, int64_t workspace_bytes, void *hip_stream);
+int dffw_op_conv_cat_backward(int device, int precision, const float *xa, int Ca, const float *xb, int Cb, int B, int N, int H, int W,
+                              const float *weight, int Cout, const float *grad_y, float *grad_xa, float *grad_xb, float *grad_w, void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

@@ -131,6 +131,8 @@ def _load():
     lib.dffw_loss_heads.argtypes = [c_int, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int64),
                                     c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_float, c_float, POINTER(c_void_p), POINTER(c_void_p),
                                     c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_heads_backward.argtypes = [c_int, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int64),
+                                        POINTER(c_void_p), POINTER(c_void_p), c_void_p]
     lib.dffw_op_conv3d_backward.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int,
                                             POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dffw_conv_wgrad_workspace_bytes.argtypes = [c_int] * 6 + [POINTER(c_int)] * 3 + [c_int]
@@ -203,6 +205,7 @@ ABI_SYMBOLS = (
     "dffw_score_conv_dgrad", "dffw_score_conv_wgrad_workspace_bytes", "dffw_score_conv_wgrad", "dffw_op_score_conv_backward",
     "dffw_adam_tensors_per_launch", "dffw_adam_step",
     "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward",
+    "dffw_heads_backward",
 )
 
 
@@ -885,7 +888,8 @@ def op_head_tail(x, w2, bn2, w4, bn4, w6, bias6, alpha, raw, *, start=0, precisi
 
 
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_tail / op_regress_heads call, in launch order."""
+    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_tail / op_regress_heads / op_heads_backward
+    call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
 
@@ -987,6 +991,49 @@ def op_loss_heads(scores, focus_dists, gt, mask, conf=None, weights=(0.3, 0.5, 0
                                    (c_float * 4)(*[float(x) for x in weights[:n]]), 0 if depth_range is None else 1, lo, hi, ptrs(pred), ptrs(grad),
                                    _ptr(losses), _ptr(ws), ws.numel(), _stream_ptr(dev)), "dffw_loss_heads")
     return losses, pred, grad
+
+
+def op_heads_backward(scores, focus_dists, grad_preds, H, W, *, out=None):
+    """dffw_heads_backward: the gradient of 1..4 regression heads (op_regress_heads) under any upstream gradient, down to the score volumes.
+    scores: fp32 (B,N,h_k,w_k) CUDA tensors with H = s*h_k, W = s*w_k, s in {1,2,4,8}; focus_dists broadcastable to (B,N,H,W), read through
+    its strides; grad_preds[k]: contiguous fp32 (B,H,W), or None for a head without a gradient (not launched).  out: optional list of
+    contiguous fp32 tensors shaped like the scores to write into (entries of skipped heads are ignored).  Enqueue-only on the current
+    stream.  Returns the list of gradients, None where grad_preds[k] is None; op_kernels() then names the launches."""
+    n = len(scores)
+    if not 1 <= n <= 4:
+        raise ValueError(f"op_heads_backward: 1 to 4 heads, got {n}")
+    if len(grad_preds) != n:
+        raise ValueError(f"op_heads_backward: {n} heads but {len(grad_preds)} upstream gradients")
+    B, N = scores[0].shape[:2]
+    device = scores[0].device
+    if device.type != "cuda":
+        raise DffwError("op_heads_backward needs GPU tensors (no CPU fallback)")
+    scores = [s.contiguous() for s in scores]
+    for s in scores:
+        if s.dtype != torch.float32 or s.dim() != 4 or s.shape[0] != B or s.shape[1] != N:
+            raise ValueError(f"score volumes must be float32 (B,N,h,w) with B={B}, N={N}; got {s.dtype} {tuple(s.shape)}")
+    if focus_dists.dtype != torch.float32 or focus_dists.device != device:
+        raise ValueError("focus_dists must be float32 on the scores' device")
+    for g in grad_preds:
+        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (B, H, W) or not g.is_contiguous() or g.device != device):
+            raise ValueError(f"upstream gradients must be contiguous float32 ({B},{H},{W}) tensors on the scores' device")
+    fd = focus_dists.expand(B, N, H, W)
+    if out is None:
+        out = [torch.empty_like(s) if g is not None else None for s, g in zip(scores, grad_preds)]
+    else:
+        if len(out) != n:
+            raise ValueError(f"out must list {n} tensors")
+        out = [o if g is not None else None for o, g in zip(out, grad_preds)]
+        for o, s in zip(out, scores):
+            if o is not None and (o.dtype != torch.float32 or o.shape != s.shape or not o.is_contiguous() or o.device != device):
+                raise ValueError("out must be contiguous float32 tensors shaped like the scores, on their device")
+    dev = _dev(scores[0])
+    ptrs = lambda ts: (c_void_p * 4)(*[t.data_ptr() if t is not None else None for t in ts])
+    with torch.cuda.device(dev):
+        _check(lib.dffw_heads_backward(dev, n, ptrs(scores), (c_int * 4)(*[s.shape[2] for s in scores]), (c_int * 4)(*[s.shape[3] for s in scores]),
+                                       B, N, H, W, _ptr(fd), (c_int64 * 4)(*fd.stride()), ptrs(grad_preds), ptrs(out), _stream_ptr(dev)),
+               "dffw_heads_backward")
+    return list(out)
 
 
 def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False):

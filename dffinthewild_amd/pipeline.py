@@ -333,6 +333,64 @@ class HeadsLoss(torch.autograd.Function):
         return tuple(g * grad_out for g in ctx.saved_tensors) + (None,) * 6
 
 
+# ---- the regression heads as a differentiable node of their own ------------------------------------------------
+def _head_scale(score, H, W):
+    """s in (1, 2, 4, 8) with (H, W) = s * the score's size: the heads the backward serves; None for any other size."""
+    h, w = score.shape[-2:]
+    return next((s for s in (1, 2, 4, 8) if h * s == H and w * s == W), None)
+
+
+class RegressHeads(torch.autograd.Function):
+    """maps = RegressHeads.apply(focus_dists, (H, W), *scores): the depth maps of 1..4 regression heads (engine.op_regress_heads, the bits of the
+    inference forward) as an autograd node; backward is engine.op_heads_backward for the heads that received a gradient.  focus_dists is
+    data: it gets no gradient.  backward_kernels: engine.op_kernels() of the last backward, read on the thread that launched it (autograd
+    runs the backward of GPU tensors on a thread of its own, and dffw_last_op_kernels is per thread, so the caller's op_kernels() cannot see it)."""
+
+    backward_kernels = []
+
+    @staticmethod
+    def forward(ctx, focus_dists, size, *scores):
+        _dev(scores[0], "score volumes")
+        H, W = size
+        if ctx.needs_input_grad[0]:
+            raise ValueError("regress_heads: focus_dists is data, it has no gradient here (requires_grad is set)")
+        for k, s in enumerate(scores):
+            if ctx.needs_input_grad[2 + k] and _head_scale(s, H, W) is None:
+                raise ValueError(f"regress_heads: scores[{k}] requires grad at {s.shape[-2]}x{s.shape[-1]}, which is not {H}x{W} divided by 1, 2, 4 "
+                                 f"or 8: the backward does not serve it")
+        ctx.set_materialize_grads(False)
+        ctx.size = (H, W)
+        ctx.save_for_backward(focus_dists, *scores)
+        return tuple(engine.op_regress_heads([s.detach().float() for s in scores], focus_dists.float(), H, W))
+
+    @staticmethod
+    def backward(ctx, *grad_maps):
+        focus_dists, *scores = ctx.saved_tensors
+        H, W = ctx.size
+        live = [k for k, (g, need) in enumerate(zip(grad_maps, ctx.needs_input_grad[2:])) if g is not None and need]
+        grads, RegressHeads.backward_kernels = [None] * len(scores), []
+        if live:   # only these heads go to the library: the others may have a size the backward does not serve
+            got = engine.op_heads_backward([scores[k].detach().float() for k in live], focus_dists.float(),
+                                           [grad_maps[k].contiguous().float() for k in live], H, W)
+            RegressHeads.backward_kernels = engine.op_kernels()
+            for k, g in zip(live, got):
+                grads[k] = g
+        return (None, None) + tuple(g.to(s.dtype) if g is not None else None for g, s in zip(grads, scores))
+
+
+def regress_heads(scores, focus_dists, size=None):
+    """The depth maps (B,H,W) of 1 to 4 score volumes (B,N,h_k,w_k) as a tuple that carries a gradient: bilinear upsample to `size` (default:
+    the largest score's size), softplus + 1e-6, normalisation over the slices, sum of focus_dists * p.  Any loss written in PyTorch on the maps
+    differentiates through the HIP backward down to the scores; heads the loss does not use are not launched.  The forward takes any
+    score size; a score that requires grad must be (H,W) divided by 1, 2, 4 or 8.  focus_dists: broadcastable to (B,N,H,W), no gradient."""
+    scores = tuple(scores)
+    if not 1 <= len(scores) <= 4:
+        raise ValueError(f"regress_heads: 1 to 4 score volumes, got {len(scores)}")
+    if size is None:
+        size = (max(s.shape[-2] for s in scores), max(s.shape[-1] for s in scores))
+    return RegressHeads.apply(focus_dists, (int(size[0]), int(size[1])), *scores)
+
+
 def _xw_backward(ctx, op, x, weight, grad, **kw):
     """(grad_x, grad_w) of a conv node whose first two inputs are x and the weight: ``op`` (an engine.op_*_backward) computes those autograd
     asks for, and the weight's gradient goes to the weight's device and dtype."""

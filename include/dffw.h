@@ -347,6 +347,22 @@ int dffw_loss_heads(int device, int n_heads, const float *const score[4], const 
                     int use_range, float lo, float hi, float *const pred[4], float *const grad[4],
                     double *losses, void *workspace, int64_t workspace_bytes, void *hip_stream);
 
+/* ---- backward of the regression heads under any upstream gradient -------------------------------------------------------
+ * dffw_heads_backward differentiates the heads of dffw_op_regress_heads on their own: given grad_pred[k] = dL/dd_k of any loss L,
+ *     dL/dv_n(i) = grad_pred(i) (f_n - d_k)/S sigmoid(v_n)  (sigmoid = 1 for v > 20),   grad_score[k] = upsample^T(dL/dv)
+ * with v, S and d_k as in dffw_loss_heads.  No mask, gt, conf or loss: those live in the caller's own graph.
+ *   score[k]       device fp32 (B,N,h[k],w[k]); H = s*h[k], W = s*w[k] with s in {1,2,4,8} (else DFFW_EINVAL)
+ *   focus_dists    device fp32, element strides fd_strides (any, 0 included) for dims (B,N,H,W)
+ *   grad_pred[k]   device fp32 (B,H,W) contiguous; a zero contributes exactly zero, NaN / Inf reach the elements the pixel's taps touch
+ *   grad_score[k]  device fp32 (B,N,h[k],w[k]) contiguous; every element is written.  N == 1: all zeros
+ * A head whose grad_pred and grad_score are both NULL is skipped; one of the two NULL is DFFW_EINVAL.  n_heads outside 1..4, a null array
+ * or score, a dimension below 1, B > 65535, H*W >= 2^31 or a head of another size: DFFW_EINVAL before the GPU is touched.
+ * Enqueue-only on hip_stream: one launch per head that has a gradient (dffw_last_op_kernels lists them), no allocation, no workspace, no
+ * atomics; the summation order is fixed, so two calls give identical bits. */
+int dffw_heads_backward(int device, int n_heads, const float *const score[4], const int h[4], const int w[4],
+                        int B, int N, int H, int W, const float *focus_dists, const int64_t fd_strides[4],
+                        const float *const grad_pred[4], float *const grad_score[4], void *hip_stream);
+
 /* ---- conv backward: data and weight gradients of the aggregation network's plain convs ------------------------------
  * Geometries (anything else, and dilation, is DFFW_EINVAL): 3x3x3 pad 1 stride 1 or (1,2,2); 1x3x3 pad (0,1,1) stride 1; the transposed
  * 3x3x3 stride (1,2,2) pad 1 output_padding (0,1,1).  Cin and Cout multiples of 8, at most 128; H and W even at stride (1,2,2).

@@ -150,11 +150,27 @@ class Network(nn.Module):
         replica._inherited_fp = fp
         return replica
 
+    def _device_state(self, idx):
+        """state_dict() if every floating entry is a contiguous float32 tensor on cuda:idx (what Engine.update takes), else None."""
+        sd = self.state_dict()
+        for t in sd.values():
+            if torch.is_floating_point(t) and not (t.is_cuda and t.device.index == idx and t.dtype == torch.float32 and t.is_contiguous()):
+                return None
+        return sd
+
     def _engine_on(self, device):
         idx = device.index if device.index is not None else torch.cuda.current_device()
         fp = self._fingerprint()
         with self._guard:
             hit = self._engines.get(idx)
+            if hit is not None and hit[0] != fp and hit[0][0] == fp[0]:
+                # same token, other version sum: parameters were changed in place (optimizer.step(), an EMA copy).  The engine
+                # repacks them on the GPU (Engine.update) when they all live there as contiguous float32; else it is rebuilt
+                sd = self._device_state(idx)
+                if sd is not None:
+                    hit[1].update(sd)
+                    hit = (fp, hit[1])
+                    self._engines[idx] = hit
             if hit is None or hit[0] != fp:
                 sd = {k: v for k, v in self.state_dict().items()}
                 hit = (fp, _engine.Engine(sd, torch.device("cuda", idx), self.precision, self._NET))

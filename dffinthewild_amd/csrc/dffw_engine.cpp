@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "dffw_repack.h"
 #include "dffw_run.h"
 #include "dffw_srd_roll.h"
 #include "dffw_stem.h"
@@ -199,6 +200,8 @@ static const Table &table_for(int net) {
     static const Table e2e = Table::e2e_net();
     return net == DFFW_NET_E2E ? e2e : depth;
 }
+
+const std::vector<LayerDef> &net_layers(int net) { return table_for(net).layers; }   // (dffw_repack.cpp)
 
 // the layers of one block as the table defines them (the single-operator entry points of dffw_ops.cpp pack them under the forward's names)
 std::vector<LayerDef> srd_layers(const std::string &p, int c) { Table t; t.srd(p, c); return t.layers; }

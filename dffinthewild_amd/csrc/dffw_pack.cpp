@@ -9,6 +9,7 @@
 #include "dffw_align.h"
 #include "dffw_srd_roll.h"
 #include "dffw_pack.h"
+#include "dffw_repack.h"
 
 namespace dffw {
 
@@ -44,6 +45,22 @@ static void host_split(int prec, float v, uint16_t &hi, uint16_t &lo) {
     }
 }
 
+// ---- plan mode (dffw_repack.h) -----------------------------------------------------
+// plan_conv runs pack_conv once more with probe weights whose bit pattern is the source index + 1 and with BatchNorm ignored: what a fragment
+// lambda returns is then the source of the slot (0.f: none).  While t_plan is set nothing is allocated or uploaded: upload() records the size of
+// each buffer, in `owned` order, with the source map the writer left in t_next (none: a buffer without weights in it).
+static thread_local LayerPlan *t_plan = nullptr;
+static thread_local BufPlan t_next;
+static int32_t src_of(float probe) {
+    uint32_t u;
+    memcpy(&u, &probe, 4);
+    return (int32_t)u - 1;
+}
+static void plan_f32(std::vector<int32_t> &&map) {
+    t_next.kind = RK_F32;
+    t_next.map = std::move(map);
+}
+
 // ---- device buffers ----------------------------------------------------------------------------
 void free_packed(PackedConv &pc) {
     for (void *p : pc.owned) (void)hipFree(p);
@@ -55,10 +72,18 @@ void free_packed(PackedConv &pc) {
 template <class T>
 static int upload(PackedConv &pc, T *&dst, const std::vector<T> &v) {
     if (dst) return dffw_fail(DFFW_EINVAL, "pack_conv: layer %s packs one device buffer twice", pc.def.conv.c_str());
+    if (t_plan) {
+        t_next.bytes = v.size() * sizeof(T);
+        t_plan->bufs.push_back(std::move(t_next));
+        t_next = BufPlan();
+        dst = reinterpret_cast<T *>(uintptr_t(64));   // never dereferenced: marks the field as packed for the check above
+        return DFFW_OK;
+    }
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, v.size() * sizeof(T));
     if (e == hipSuccess) {
         pc.owned.push_back(p);
+        pc.owned_bytes.push_back(v.size() * sizeof(T));
         e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return dffw_fail(DFFW_EHIP, "pack_conv: upload of %zu bytes -> %s", v.size() * sizeof(T), hipGetErrorString(e));
@@ -72,6 +97,14 @@ template <class W>
 static int pack_frags(PackedConv &pc, uint16_t *&dst, int prec, int nfrag, W &&w) {
     const int parts = prec_parts(prec);
     std::vector<uint16_t> buf((size_t)nfrag * parts * 512, 0);
+    if (t_plan) {
+        t_next.kind = RK_FRAGS;
+        t_next.map.resize((size_t)nfrag * 512);
+        for (int f = 0; f < nfrag; ++f)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) t_next.map[(size_t)f * 512 + (size_t)lane * 8 + j] = src_of(w(f, lane, j));
+        return upload(pc, dst, buf);
+    }
     for (int f = 0; f < nfrag; ++f)
         for (int lane = 0; lane < 64; ++lane)
             for (int j = 0; j < 8; ++j) {
@@ -99,10 +132,13 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
     const int c8n = cin_pad / 8;
     pc.cin_all = cin_pad;
     int rc = DFFW_OK;
+    const bool plan = t_plan != nullptr;   // plan mode: `weight` / `shortcut_w` are probes, `bn` / `conv_bias` only say whether the layer has them
+    const int64_t n_w = (int64_t)L.cin * L.cout * L.kd * L.kh * L.kw, n_sc = shortcut_w ? (int64_t)L.cout * shortcut_cin : 0;
+    const int32_t shift_at = (int32_t)(n_w + n_sc), cbias_at = shift_at + L.cout;   // where the repack scratch holds shift[c] and the raw conv bias
 
     // fold BatchNorm (eval mode, eps 1e-5): y = conv(x)*scale + shift
     std::vector<double> scale(L.cout, 1.0), shift(L.cout, 0.0);
-    for (int c = 0; c < L.cout; ++c) {
+    for (int c = 0; c < L.cout && !plan; ++c) {
         if (bn) {
             const double g = bn[c], b = bn[L.cout + c], m = bn[2 * L.cout + c], v = bn[3 * L.cout + c];
             scale[c] = g / std::sqrt(v + 1e-5);
@@ -112,10 +148,20 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
     }
     std::vector<float> bias(pc.nt * 16, 0.f);
     for (int c = 0; c < L.cout; ++c) bias[c] = (float)shift[c];
+    if (plan) {
+        std::vector<int32_t> m(bias.size(), -1);
+        for (int c = 0; c < L.cout; ++c) m[c] = shift_at + c;
+        plan_f32(std::move(m));
+    }
     if ((rc = upload(pc, pc.bias, bias))) return rc;
     if (L.cout == 8 && pc.nt == 1) {   // pixel-pair kernels: rows 8-15 are the second pixel's 8 channels
         std::vector<float> b2(16);
         for (int c = 0; c < 16; ++c) b2[c] = (float)shift[c & 7];
+        if (plan) {
+            std::vector<int32_t> m(16);
+            for (int c = 0; c < 16; ++c) m[c] = shift_at + (c & 7);
+            plan_f32(std::move(m));
+        }
         if ((rc = upload(pc, pc.bias_pair, b2))) return rc;
     }
 
@@ -163,6 +209,7 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
         if (cin >= L.cin) return 0.f;
         const int64_t kidx = ((int64_t)t.kz * L.kh + t.ky) * L.kw + t.kx;
         const int64_t i = L.transposed ? ((int64_t)cin * L.cout + cout) * kvol + kidx : ((int64_t)cout * L.cin + cin) * kvol + kidx;
+        if (plan) return weight[i];
         return (float)((double)weight[i] * scale[cout]);
     };
 
@@ -199,14 +246,25 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
         for (int kz = 0; kz < L.kd; ++kz)
             for (int ci = 0; ci < L.cin; ++ci)
                 for (int co = 0; co < L.cout; ++co) w32[((size_t)kz * L.cin + ci) * L.cout + co] = wval(co, ci, Tap{0, 0, 0, kz, 0, 0});
+        if (plan) {
+            std::vector<int32_t> m(w32.size());
+            for (size_t i = 0; i < w32.size(); ++i) m[i] = src_of(w32[i]);
+            plan_f32(std::move(m));
+        }
         if ((rc = upload(pc, pc.w32, w32))) return rc;
     }
 
     if (!L.transposed && L.bias && !bn && conv_bias && L.cout == 3 && L.kd == 1 && L.kh == 3 && L.kw == 3 && L.sh == 1 && L.ph == 1 && L.pw == 1 &&
         L.dh == 1 && L.cin % 8 == 0 && L.cin <= 64 && !shortcut_w) {
         std::vector<float> wh((size_t)3 * L.cin * 9 + 3);
-        memcpy(wh.data(), weight, (size_t)3 * L.cin * 9 * sizeof(float));      // PyTorch (3, cin, 1, 3, 3) is already [c][ci][dy][dx]
-        memcpy(wh.data() + (size_t)3 * L.cin * 9, conv_bias, 3 * sizeof(float));
+        if (plan) {   // the raw weights (no BatchNorm: the folded ones are the same bits) and the raw bias
+            std::vector<int32_t> m(wh.size());
+            for (size_t i = 0; i < m.size(); ++i) m[i] = i < (size_t)n_w ? (int32_t)i : cbias_at + (int32_t)(i - n_w);
+            plan_f32(std::move(m));
+        } else {
+            memcpy(wh.data(), weight, (size_t)3 * L.cin * 9 * sizeof(float));      // PyTorch (3, cin, 1, 3, 3) is already [c][ci][dy][dx]
+            memcpy(wh.data() + (size_t)3 * L.cin * 9, conv_bias, 3 * sizeof(float));
+        }
         if ((rc = upload(pc, pc.whead, wh))) return rc;
     }
 
@@ -439,6 +497,14 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
     // The attention fragments below do not follow the common layout: their 1x1x1 forms carry a low half for j < 4 only, and the
     // 32-channel form interleaves parts with output tiles.  put() splits one value into wr[hi_at] and, where the form has one, wr[lo_at].
     auto put = [&](std::vector<uint16_t> &wr, size_t hi_at, size_t lo_at, bool has_lo, float val) {
+        if (plan) {   // one entry per 16-bit slot: 2 * source + part
+            const int32_t src = src_of(val);
+            t_next.kind = RK_SLOTS;
+            if (t_next.map.size() != wr.size()) t_next.map.assign(wr.size(), -1);
+            t_next.map[hi_at] = src < 0 ? -1 : 2 * src;
+            if (parts == 2 && has_lo) t_next.map[lo_at] = src < 0 ? -1 : 2 * src + 1;
+            return;
+        }
         uint16_t hi, lo;
         host_split(prec, val, hi, lo);
         wr[hi_at] = hi;
@@ -636,6 +702,35 @@ int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn,
         };
         if ((rc = pack_frags(pc, pc.wroll_t, prec, ROLL_CHUNKS_T, frag))) return rc;
     }
+    return DFFW_OK;
+}
+
+int plan_conv(const LayerDef &def, int prec, int shortcut_cin, LayerPlan &out) {
+    out = LayerPlan();
+    out.n_w = (int64_t)def.cin * def.cout * def.kd * def.kh * def.kw;
+    out.n_sc = shortcut_cin > 0 ? (int64_t)def.cout * shortcut_cin : 0;
+    out.cout = def.cout;
+    out.has_bias = def.bias;
+    if (out.scratch_floats() >= (1 << 30)) return dffw_fail(DFFW_EINVAL, "plan_conv: layer %s is too large for 31-bit source indices", def.conv.c_str());
+    std::vector<float> probe((size_t)(out.n_w + out.n_sc));
+    for (size_t i = 0; i < probe.size(); ++i) {
+        const uint32_t u = (uint32_t)i + 1;
+        memcpy(&probe[i], &u, 4);
+    }
+    const float present = 0.f;   // bn / conv_bias are not read in plan mode: only whether the layer has them
+    PackedConv tmp;
+    t_next = BufPlan();
+    t_plan = &out;
+    const int rc = pack_conv(def, prec, probe.data(), def.bn.empty() ? nullptr : &present, def.bias ? &present : nullptr, tmp,
+                             out.n_sc ? probe.data() + out.n_w : nullptr, shortcut_cin);
+    t_plan = nullptr;
+    t_next = BufPlan();
+    if (rc) return rc;
+    const int64_t n_src = out.scratch_floats();
+    for (const BufPlan &b : out.bufs)
+        for (int32_t m : b.map)
+            if (m < -1 || (b.kind == RK_SLOTS ? m >> 1 : m) >= n_src)
+                return dffw_fail(DFFW_EINVAL, "plan_conv: layer %s has a source index outside its %lld sources", def.conv.c_str(), (long long)n_src);
     return DFFW_OK;
 }
 

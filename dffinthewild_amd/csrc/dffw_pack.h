@@ -55,6 +55,7 @@ struct TilePack {            // weights/taps in conv_tile's order (per pass: [st
 struct PackedConv {
     LayerDef def;
     std::vector<void *> owned;
+    std::vector<size_t> owned_bytes;   // size of owned[i]
     int nt = 1;
     float *bias = nullptr;  // device, nt*16 floats
     std::vector<Variant> variants;

@@ -96,9 +96,15 @@ struct ProfRec {
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
+namespace dffw {
+struct RepackPlan;   // dffw_repack.h: where every slot of every packed buffer comes from (built at the first dffw_engine_update)
+void free_repack_plan(RepackPlan *p);
+}  // namespace dffw
+
 struct dffw_engine {
     int device = 0, net = 0, prec = 0;
     std::map<std::string, dffw::PackedConv> convs;
+    dffw::RepackPlan *repack = nullptr;
     bool profiling = false;
     std::vector<ProfRec> recs;
     uint16_t *zero_page = nullptr;  // 256 zero bytes: what out-of-volume LDS-DMA lanes read
@@ -134,6 +140,7 @@ struct dffw_engine {
         for (int i = 0; i < NEV; ++i)
             if (ev[i]) (void)hipEventDestroy(ev[i]);
         for (auto &kv : convs) dffw::free_packed(kv.second);
+        dffw::free_repack_plan(repack);
     }
 };
 

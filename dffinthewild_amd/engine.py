@@ -70,6 +70,11 @@ def _load():
     lib.dffw_engine_destroy.argtypes = [c_void_p]
     lib.dffw_engine_destroy.restype = None
     lib.dffw_engine_precision.argtypes = [c_void_p]
+    lib.dffw_engine_update.argtypes = [c_void_p, POINTER(_Tensor), c_int, c_void_p]
+    lib.dffw_engine_repack_stats.argtypes = [c_void_p, POINTER(c_int64)]
+    lib.dffw_engine_packed_bytes.argtypes = [c_void_p]
+    lib.dffw_engine_packed_bytes.restype = c_int64
+    lib.dffw_engine_packed_read.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.dffw_workspace_bytes.restype = c_int64
     fwd = [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int, c_int, c_int, c_int,
@@ -206,6 +211,7 @@ ABI_SYMBOLS = (
     "dffw_adam_tensors_per_launch", "dffw_adam_step",
     "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward",
     "dffw_heads_backward",
+    "dffw_engine_update", "dffw_engine_repack_stats", "dffw_engine_packed_bytes", "dffw_engine_packed_read",
 )
 
 
@@ -272,6 +278,7 @@ class Engine:
         _check(lib.dffw_engine_create(self.index, net, arr, i, PRECISIONS[precision], byref(self._h)), "dffw_engine_create")
         self._ws = {}
         self._ws_stream = None      # torch stream the cached workspace was last used on
+        self._upd_stream = None     # torch stream of an update() that no forward has been ordered behind yet
         self._lock = threading.Lock()
 
     # an Engine owns a dffw_engine* and a device workspace: a second owner would free the handle twice
@@ -319,6 +326,7 @@ class Engine:
         the engine's allocation path also depends on its DFFW_* switches (read per call): if it reports the workspace too
         small (-3) the size is asked for again under the present switches and the forward repeated once."""
         cur = torch.cuda.current_stream(self.index)
+        self._after_update(cur)
         if self._ws_stream is not None and self._ws_stream != cur and self._ws:
             # the workspace is one buffer shared by successive forwards: a forward issued under another torch stream must
             # not start before the previous one (on the old stream) is done with it
@@ -334,6 +342,67 @@ class Engine:
             self._ws.clear()
             rc = call(self._workspace(B, N, H, W, extra))
         return rc
+
+    def _after_update(self, cur):
+        """A forward issued under another torch stream than the last update() must not read the packed weights before the repack kernels
+        have written them."""
+        if self._upd_stream is not None and self._upd_stream != cur:
+            ev = torch.cuda.Event()
+            ev.record(self._upd_stream)
+            cur.wait_event(ev)
+        self._upd_stream = None
+
+    def update(self, state_dict):
+        """Repack the weights from ``state_dict`` (the module's own tensors after ``optimizer.step()`` or an in-place edit) on the GPU:
+        dffw_engine_update folds BatchNorm and rewrites every operand buffer by two kernels on the current stream, bit for bit what a new
+        ``Engine(state_dict)`` would hold.  Every floating entry must be a contiguous float32 CUDA tensor on this engine's device (no host
+        round trip, no silent copy): anything else raises.  Enqueue-only after the first call, which builds the engine's repack plan."""
+        keep, arr = [], (_Tensor * len(state_dict))()
+        i = 0
+        for key, t in state_dict.items():
+            if not torch.is_tensor(t):
+                raise ValueError(f"Engine.update: '{key}' is not a tensor")
+            if not torch.is_floating_point(t):
+                continue  # num_batches_tracked counters carry no arithmetic
+            if not t.is_cuda or _dev(t) != self.index:
+                raise ValueError(f"Engine.update: '{key}' is on {t.device}, the engine repacks from tensors on cuda:{self.index} "
+                                 "(build a new Engine from a CPU state dict)")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"Engine.update: '{key}' must be a contiguous float32 tensor, got {t.dtype}"
+                                 f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+            t = t.detach()
+            keep.append(t)
+            arr[i] = _Tensor(key.encode(), _f32(t), t.numel())
+            i += 1
+        with self._lock, torch.cuda.device(self.index):
+            cur = torch.cuda.current_stream(self.index)
+            if self._ws_stream is not None and self._ws_stream != cur:
+                # the last forward (on the old stream) may still read the buffers this call rewrites
+                ev = torch.cuda.Event()
+                ev.record(self._ws_stream)
+                cur.wait_event(ev)
+            self._after_update(cur)
+            _check(lib.dffw_engine_update(self._h, arr, i, _stream_ptr(self.index)), "dffw_engine_update")
+            self._upd_stream = cur
+            if cur != torch.cuda.default_stream(self.index):
+                for t in keep:   # the kernels read the tensors when the stream gets to them: the caching allocator must not hand their memory on before
+                    t.record_stream(cur)
+
+    def repack_stats(self):
+        """{plan_bytes, fold_bytes, map_bytes, buffer_bytes} of the repack plan (it exists after the first update())."""
+        out = (c_int64 * 4)()
+        _check(lib.dffw_engine_repack_stats(self._h, out), "dffw_engine_repack_stats")
+        return dict(zip(("plan_bytes", "fold_bytes", "map_bytes", "buffer_bytes"), out))
+
+    def packed_bytes(self):
+        """Every packed device buffer of the engine, concatenated in a fixed order (layer name, then packing order), as a uint8 CPU tensor
+        (tests compare an updated engine with a newly built one)."""
+        with self._lock, torch.cuda.device(self.index):
+            torch.cuda.synchronize(self.index)
+            n = _check(lib.dffw_engine_packed_bytes(self._h), "dffw_engine_packed_bytes")
+            out = torch.empty(n, dtype=torch.uint8)
+            _check(lib.dffw_engine_packed_read(self._h, c_void_p(out.data_ptr()), n, _stream_ptr(self.index)), "dffw_engine_packed_read")
+        return out
 
     def forward(self, FS, focus_dists, taps=None):
         """FS (B,3,N,H,W) float32 on this engine's device; focus_dists broadcastable to (B,N,H,W).

@@ -705,6 +705,9 @@ class Adam(torch.optim.Optimizer):
             for (_, t), rs in calls.items():
                 ps, gs, ms, vs, _ = zip(*rs)
                 engine.op_adam_step(ps, gs, ms, vs, step=t, lr=group["lr"], betas=group["betas"], eps=group["eps"])
+                # the kernel wrote through raw pointers: count the in-place change as torch.optim.Adam's own updates do, so that whoever
+                # watches the parameters' versions (Network's packed-weight cache) sees the step
+                torch.autograd.graph.increment_version(ps)
             bump()   # counted once the updates are enqueued: a refused call leaves the counts as they were
         return None
 

@@ -82,6 +82,25 @@ int dffw_engine_create(int device, int net, const dffw_tensor *tensors, int n_te
 void dffw_engine_destroy(dffw_engine *e);
 int dffw_engine_precision(const dffw_engine *e);
 
+/* Repack the engine's weights from parameters that live on its GPU (after an optimiser step or any in-place edit): BatchNorm folding and every
+ * operand layout dffw_engine_create wrote, by two kernels (dffw::repack_fold_kernel, dffw::repack_gather_kernel) on hip_stream.  The packed bytes
+ * are exactly those of a dffw_engine_create from the same values.  tensors: as for dffw_engine_create, but `data` are DEVICE pointers on the
+ * engine's device, fp32, contiguous; they must stay valid until the stream has run the kernels.  Every name the live layers need is looked up,
+ * with its element count and a null check, before the first launch: on any refusal (DFFW_EMISSING; DFFW_EINVAL for a null engine, null tensors,
+ * a wrong element count or a null pointer) nothing is enqueued and the engine is unchanged.  The first call builds the engine's repack plan
+ * (allocates and copies); from the second on the call is enqueue-only: no allocation, no copy, no synchronisation, no atomics, and two calls with
+ * the same values give the same bytes.  The caller orders the stream behind forwards that still read the weights. */
+int dffw_engine_update(dffw_engine *e, const dffw_tensor *tensors, int n_tensors, void *hip_stream);
+/* Test side: the engine's packed device buffers, concatenated in a fixed order (layer name, then the order the packer wrote them in).
+ * dffw_engine_packed_bytes: their total size.  dffw_engine_packed_read: copies them to host_dst (capacity >= that size) after a synchronise of
+ * hip_stream.  A null engine or destination, or a short capacity: DFFW_EINVAL. */
+/* What the engine's repack plan holds and moves, once the first dffw_engine_update has built it (before: DFFW_EINVAL): out[0] device bytes of
+ * the plan (scratch, source maps, job table); out[1] bytes the fold launches read and write; out[2] bytes of source maps and out[3] bytes of
+ * operand buffers one gather launch reads and writes. */
+int dffw_engine_repack_stats(const dffw_engine *e, int64_t out[4]);
+int64_t dffw_engine_packed_bytes(const dffw_engine *e);
+int dffw_engine_packed_read(dffw_engine *e, void *host_dst, int64_t capacity, void *hip_stream);
+
 /* Bytes of scratch the engine's forward (dffw_forward for DFFW_NET_DEPTH, dffw_forward_e2e for
  * DFFW_NET_E2E) needs for one (B,N,H,W) call; the caller allocates it (torch's caching allocator in the
  * Python binding) so nothing is hipMalloc'ed per call. */

@@ -120,7 +120,7 @@ static bool head_warp_ok(const Run &r, const PackedConv *cur, const Act &fe) {
 
 // the head's first conv over [warped ref | warped cur | flow] of the level features (consumed): head_warp on the split filter, the split
 // filter over a [cur | flow] volume, or the whole filter over the whole volume.  `label` names the level in the profile ("flow.conv1")
-static Act head_first_conv(Run &r, const std::string &hp, const std::string &label, Act &fe, const float *alpha, const float *fov) {
+Act head_first_conv(Run &r,const std::string &hp, const std::string &label, Act &fe, const float *alpha, const float *fov) {
     const int prec = r.e->prec, B = fe.B, N = fe.N;
     ConvOpt rl; rl.relu = 1;
     char kn[64];

@@ -773,25 +773,7 @@ int dffw_engine_create(int device, int net, const dffw_tensor *tensors, int n_te
         PackedConv &pc = e->convs[L.conv];
         rc = pack_conv(L, precision, w, bn.empty() ? nullptr : bn.data(), cb, pc, sw, scin);
         if (rc) return rc;
-        if (L.head_split > 0 && !bn.empty()) {
-            // conv over [ref | cur | flow] = conv_ref(ref) + conv_cur([cur | flow]) (linearity): the ref part is the same for
-            // every slice of a sample, so it is computed once per sample and added as a slice-broadcast residual
-            const int C = L.head_split, kv = L.kd * L.kh * L.kw;
-            auto slice = [&](int c0, int c1) {
-                std::vector<float> ws((size_t)L.cout * (c1 - c0) * kv);
-                for (int co = 0; co < L.cout; ++co)
-                    memcpy(ws.data() + (size_t)co * (c1 - c0) * kv, w + ((size_t)co * L.cin + c0) * kv, (size_t)(c1 - c0) * kv * sizeof(float));
-                return ws;
-            };
-            LayerDef Lr = L, Lc = L;
-            Lr.conv = L.conv + "#ref"; Lr.cin = C; Lr.head_split = 0;
-            Lc.conv = L.conv + "#cur"; Lc.cin = L.cin - C; Lc.head_split = 0;
-            std::vector<float> bn_scale_only = bn;                       // gamma | beta | mean | var with beta = mean = 0: no shift
-            for (int c = 0; c < L.cout; ++c) bn_scale_only[L.cout + c] = bn_scale_only[2 * L.cout + c] = 0.f;
-            const std::vector<float> wr = slice(0, C), wc = slice(C, L.cin);
-            if ((rc = pack_conv(Lr, precision, wr.data(), bn_scale_only.data(), nullptr, e->convs[Lr.conv]))) return rc;
-            if ((rc = pack_conv(Lc, precision, wc.data(), bn.data(), nullptr, e->convs[Lc.conv]))) return rc;
-        }
+        if (L.head_split > 0 && !bn.empty() && (rc = pack_head_split(L, precision, w, bn.data(), e->convs[L.conv + "#ref"], e->convs[L.conv + "#cur"]))) return rc;
     }
     *out = e.release();
     return DFFW_OK;

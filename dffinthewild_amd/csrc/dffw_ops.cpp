@@ -1,7 +1,7 @@
 // The single-operator entry points of libdffw.so (dffw_op_*, include/dffw.h): one kernel family on fp32 NCDHW tensors, for the per-element
 // bounds and the kernel-name assertions of the GPU tests.  Test-only: the forward never comes here.  Every op that moves tensors is a body
 // on one shell (run_op): the body allocates from a Run's arena, stages its inputs into activation records, runs the graph's own code on
-// them (Run::conv, srd(), efd(), of_block(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
+// them (Run::conv, srd(), efd(), of_block(), head_first_conv(), head_tail(), the record-form ABIs of dffw_grad.cpp / dffw_bn.cpp / dffw_pool_grad.cpp) and stages the outputs back.
 #include <functional>
 #include <string>
 #include <vector>
@@ -341,6 +341,31 @@ int dffw_op_head_tail(int device, int precision, const float *x, int B, int C, i
         Act in = stage_in(r, x, B, C, N, H, W);
         if (start == 0) head_tail(r, hp, label, in, alpha, raw);
         else head_tail_stored(r, hp, label, in, alpha, raw);
+    });
+}
+
+// The front half of one alpha head through the graph's own head_first_conv(): fe warped by (alpha, fov), [ref | cur | flow] through conv .0.0,
+// packed (whole and as its #ref / #cur halves) under the names of the head C selects.
+int dffw_op_head_front(int device, int precision, const float *fe, int B, int C, int N, int H, int W, const float *w0, const float *bn0,
+                       const float *alpha, const float *fov, float *y0, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!fe || !w0 || !bn0 || !alpha || !fov || !y0) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (C != 8 && C != 16 && C != 32) return fail(DFFW_EINVAL, "the alpha heads take level features of 8, 16 or 32 channels, got %d", C);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    HIPCHK(hipSetDevice(device));
+    const char *head = C == 8 ? "conv3" : C == 16 ? "conv2" : "conv1";
+    const std::string hp = std::string("optical_flow_aggregation.") + head, label = std::string("flow.") + head;
+    OpEngine eng(device, precision);
+    for (const LayerDef &L : alpha_head_layers(hp, 2 * C + 2, 2 * C)) {   // as dffw_engine_create packs them; the other convs are not this op's
+        if (L.conv != hp + ".0.0") continue;
+        int rc = pack_conv(L, precision, w0, bn0, nullptr, eng.convs[L.conv]);
+        if (!rc && L.head_split > 0) rc = pack_head_split(L, precision, w0, bn0, eng.convs[L.conv + "#ref"], eng.convs[L.conv + "#cur"]);
+        if (rc) return rc;
+    }
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act in = stage_in(r, fe, B, C, N, H, W);
+        stage_out(r, head_first_conv(r, hp, label, in, alpha, fov), y0);
     });
 }
 

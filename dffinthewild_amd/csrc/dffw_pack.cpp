@@ -734,4 +734,24 @@ int plan_conv(const LayerDef &def, int prec, int shortcut_cin, LayerPlan &out) {
     return DFFW_OK;
 }
 
+// conv over [ref | cur | flow] = conv_ref(ref) + conv_cur([cur | flow]) (linearity): the ref part is the same for
+// every slice of a sample, so it is computed once per sample and added as a slice-broadcast residual
+int pack_head_split(const LayerDef &L, int prec, const float *weight, const float *bn, PackedConv &ref, PackedConv &cur) {
+    const int C = L.head_split, kv = L.kd * L.kh * L.kw;
+    auto slice = [&](int c0, int c1) {
+        std::vector<float> ws((size_t)L.cout * (c1 - c0) * kv);
+        for (int co = 0; co < L.cout; ++co)
+            memcpy(ws.data() + (size_t)co * (c1 - c0) * kv, weight + ((size_t)co * L.cin + c0) * kv, (size_t)(c1 - c0) * kv * sizeof(float));
+        return ws;
+    };
+    LayerDef Lr = L, Lc = L;
+    Lr.conv = L.conv + "#ref"; Lr.cin = C; Lr.head_split = 0;
+    Lc.conv = L.conv + "#cur"; Lc.cin = L.cin - C; Lc.head_split = 0;
+    std::vector<float> bn_scale_only(bn, bn + 4 * (size_t)L.cout);   // gamma | beta | mean | var with beta = mean = 0: no shift
+    for (int c = 0; c < L.cout; ++c) bn_scale_only[L.cout + c] = bn_scale_only[2 * L.cout + c] = 0.f;
+    const std::vector<float> wr = slice(0, C), wc = slice(C, L.cin);
+    if (int rc = pack_conv(Lr, prec, wr.data(), bn_scale_only.data(), nullptr, ref)) return rc;
+    return pack_conv(Lc, prec, wc.data(), bn, nullptr, cur);
+}
+
 }  // namespace dffw

@@ -91,5 +91,8 @@ void free_packed(PackedConv &pc);
 // shortcut_w: (cout, shortcut_cin) weights of a folded 1x1x1 shortcut over a second input, or null.
 int pack_conv(const LayerDef &L, int prec, const float *weight, const float *bn, const float *conv_bias,
               PackedConv &pc, const float *shortcut_w = nullptr, int shortcut_cin = 0);
+// The two halves of a layer with head_split > 0 (and a BatchNorm): `ref` = "<name>#ref" over the first head_split input channels with the
+// BatchNorm scale only, `cur` = "<name>#cur" over the rest with the whole BatchNorm.  weight, bn: the whole layer's, as for pack_conv.
+int pack_head_split(const LayerDef &L, int prec, const float *weight, const float *bn, PackedConv &ref, PackedConv &cur);
 
 }  // namespace dffw

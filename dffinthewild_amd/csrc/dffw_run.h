@@ -586,6 +586,9 @@ int run_depth(Run &r, const float *FS, const float *fd, const int64_t fst[4], in
 int run_e2e(Run &r, const float *FS, const float *fd, const int64_t fst[4], const float *fov, int B, int N, int H, int W, float *const out[4], float *aligned);
 Act of_block(Run &r, const std::string &p, const Act &x);
 Act of_first_block(Run &r, const std::string &p0, const float *FS, int B, int N, int H, int W);
+// the first conv of an alpha head `hp` over [warped ref | warped cur | flow] of the level features fe (consumed), warped by alpha (B,3,N) and
+// fov (B,N): y0 = relu(BN(conv)), in the warp, split or whole form (dffw_align.cpp)
+Act head_first_conv(Run &r, const std::string &hp, const std::string &label, Act &fe, const float *alpha, const float *fov);
 // an alpha head `hp` from its first conv's output y0 (consumed) to alpha += damped plane means, rawh = the undamped ones (`label` names the
 // level in the profile); head_tail_stored: its end alone, from a stored y2 (consumed)
 void head_tail(Run &r, const std::string &hp, const std::string &label, Act &y0, float *alpha, float *rawh);

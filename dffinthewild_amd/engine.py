@@ -98,6 +98,7 @@ def _load():
     lib.dffw_op_efd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 4 + [c_int, c_void_p, c_void_p]
     lib.dffw_op_of_block.argtypes = [c_int, c_int, c_void_p] + [c_int] * 7 + [POINTER(c_float)] * 5 + [c_void_p] * 2
     lib.dffw_op_head_tail.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [POINTER(c_float)] * 6 + [c_int] + [c_void_p] * 3
+    lib.dffw_op_head_front.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [POINTER(c_float)] * 2 + [c_void_p] * 4
     lib.dffw_last_op_kernels.restype = c_char_p
     lib.dffw_op_fov_warp.argtypes = [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_void_p]
@@ -196,7 +197,7 @@ ABI_SYMBOLS = (
     "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
     "dffw_op_regress_heads",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
-    "dffw_op_of_block", "dffw_op_head_tail",
+    "dffw_op_of_block", "dffw_op_head_tail", "dffw_op_head_front",
     "dffw_forward_raw", "dffw_pack_stack", "dffw_augment_stack", "dffw_unpack_stack", "dffw_colorize", "dffw_jet_lut", "dffw_metrics_scratch_bytes", "dffw_metrics",
     "dffw_comm_unique_id", "dffw_comm_init_rank", "dffw_comm_init_all", "dffw_comm_destroy", "dffw_comm_rank", "dffw_comm_size",
     "dffw_allgather", "dffw_comm_group_start", "dffw_comm_group_end", "dffw_probe_peaks",
@@ -956,8 +957,34 @@ def op_head_tail(x, w2, bn2, w4, bn4, w6, bias6, alpha, raw, *, start=0, precisi
                                      _ptr(alpha), _ptr(raw), _stream_ptr(dev)), "dffw_op_head_tail")
 
 
+def op_head_front(fe, w0, bn0, alpha, fov, *, precision="bf16x3", out=None):
+    """The front half of one alpha head (dffw_op_head_front) through the forward's dispatch: ``fe`` (B,C,N,H,W) float32 on the GPU, C = 8, 16 or
+    32, the level features; ``w0`` (2C,2C+2,1,3,3) in PyTorch layout with ``bn0`` = (gamma, beta, mean, var); ``alpha`` (B,3,N) and ``fov`` (B,N)
+    float32 on the GPU.  Returns y0 = relu(BN(conv([warp(fe)[N-1] | warp(fe)[n] | flow]))), (B,2C,N,H,W), written into ``out`` when given (a
+    contiguous float32 GPU tensor of that shape).  op_kernels() then lists the launches."""
+    if fe.device.type != "cuda" or alpha.device != fe.device or fov.device != fe.device:
+        raise DffwError("op_head_front needs GPU tensors (no CPU fallback)")
+    if fe.dim() != 5:
+        raise ValueError("op_head_front: fe must have 5 dimensions")
+    B, C, N, H, W = fe.shape
+    if tuple(w0.shape) != (2 * C, 2 * C + 2, 1, 3, 3):
+        raise ValueError(f"op_head_front: w0 must be ({2 * C},{2 * C + 2},1,3,3), got {tuple(w0.shape)}")
+    fe = fe.detach().float().contiguous()
+    a = alpha.detach().reshape(B, 3, N).float().contiguous()
+    f = fov.detach().reshape(B, N).float().contiguous()
+    y0 = torch.empty((B, 2 * C, N, H, W), dtype=torch.float32, device=fe.device) if out is None else out
+    if y0.dtype != torch.float32 or tuple(y0.shape) != (B, 2 * C, N, H, W) or not y0.is_contiguous() or y0.device != fe.device:
+        raise ValueError(f"op_head_front: out must be a contiguous float32 ({B},{2 * C},{N},{H},{W}) tensor on fe's device")
+    host = [_host_f32(w0), _bn_host(bn0)]
+    dev = _dev(fe)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_head_front(dev, PRECISIONS[precision], _ptr(fe), B, C, N, H, W, *[_f32(t) for t in host], _ptr(a), _ptr(f), _ptr(y0),
+                                      _stream_ptr(dev)), "dffw_op_head_front")
+    return y0
+
+
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_tail / op_regress_heads / op_heads_backward
+    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_front / op_head_tail / op_regress_heads / op_heads_backward
     call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
@@ -1105,15 +1132,19 @@ def op_heads_backward(scores, focus_dists, grad_preds, H, W, *, out=None):
     return list(out)
 
 
-def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False):
+def op_fov_warp(x, alpha, fovs, compat_batch_alpha0=False, out=None, flow=None):
     """FlowNetwork.FOV_warp of the reference's End_to_End path (End_to_End.py:106-134) on the GPU.
-    x (B,C,N,H,W), alpha (B,3,N,1,1) or (B,3,N), fovs (B,1,N,1,1) or (B,N); returns (warped, flow (B,2,N,H,W))."""
+    x (B,C,N,H,W), alpha (B,3,N,1,1) or (B,3,N), fovs (B,1,N,1,1) or (B,N); returns (warped, flow (B,2,N,H,W)), written into ``out`` /
+    ``flow`` when given (contiguous float32 GPU tensors of those shapes)."""
     B, C, N, H, W = x.shape
     x = x.contiguous()
     a = alpha.reshape(B, 3, N).contiguous().float()
     f = fovs.reshape(B, N).contiguous().float()
-    out = torch.empty_like(x)
-    flow = torch.empty((B, 2, N, H, W), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x) if out is None else out
+    flow = torch.empty((B, 2, N, H, W), dtype=torch.float32, device=x.device) if flow is None else flow
+    for t, shape, what in ((out, (B, C, N, H, W), "out"), (flow, (B, 2, N, H, W), "flow")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"op_fov_warp: {what} must be a contiguous float32 {shape} tensor on x's device")
     dev = _dev(x)
     with torch.cuda.device(dev):
         _check(lib.dffw_op_fov_warp(dev, _ptr(x), B, C, N, H, W, _ptr(a), _ptr(f), int(compat_batch_alpha0), _ptr(out), _ptr(flow), _stream_ptr(dev)),

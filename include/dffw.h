@@ -222,7 +222,18 @@ int dffw_op_head_tail(int device, int precision, const float *x, int B, int C, i
                       const float *w4, const float *bn4, const float *w6, const float *bias6, int start, float *alpha, float *raw,
                       void *hip_stream);
 
-/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_op_head_tail / dffw_op_regress_heads / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
+/* The front half of one alpha head of the alignment network (End_to_End.py:77-101) through the forward's own dispatch: the level features
+ * warped by the parameters accumulated so far (FOV_warp, bilinear in the plane, zeros outside) and the head's first conv over them,
+ *   y0[b,:,n] = relu(BN(conv1x3x3([warp(fe)[b,:,N-1] | warp(fe)[b,:,n] | flow_x, flow_y of slice n], w0))),
+ * as head_warp_kernel on the split filter, as the split filter over a [cur | flow] volume, or as the whole filter over the whole volume
+ * (whichever the shape and the switches select).  Test-only.  C = 8, 16 or 32 selects the head (conv3, conv2, conv1) and the layer names the
+ * filter is packed under.  fe: device fp32 (B,C,N,H,W); w0: host fp32 (2C,2C+2,1,3,3) with bn0 (4*2C values gamma|beta|mean|var); alpha:
+ * device fp32 (B,3,N) (scale offset, x shift, y shift); fov: device fp32 (B,N); y0: device fp32 (B,2C,N,H,W).  Refused with DFFW_EINVAL
+ * before any GPU call: a null pointer, an unknown precision, C outside {8, 16, 32}, a size below 1. */
+int dffw_op_head_front(int device, int precision, const float *fe, int B, int C, int N, int H, int W, const float *w0, const float *bn0,
+                       const float *alpha, const float *fov, float *y0, void *hip_stream);
+
+/* Kernel names of every launch of the calling thread's last dffw_op_srd / dffw_op_efd / dffw_op_of_block / dffw_op_head_front / dffw_op_head_tail / dffw_op_regress_heads / dffw_sim_render / dffw_augment_stack call, in launch order, joined by
  * ';' (as dffw_profile_collect spells them); "" before any, or after a call that failed before launching. */
 const char *dffw_last_op_kernels(void);
 

@@ -15,6 +15,73 @@ struct RollArgs {
     const float *bias2;      // ... and its BatchNorm shift (added to a.bias in the accumulator init)
 };
 
+// ---- the slice stream of a rolling kernel (the one place that decides it; tools/roll_stream_model.cpp replays it on the CPU) ----
+// The units of a workgroup form ONE stream of input slices, every one of them a real slice of the volume: a unit over output slices [zbeg, zbeg + nz)
+// of `ni` contributes its own nz slices, one halo slice in front when zbeg > 0 (`lead`) and one behind when zbeg + nz < ni (`trail`).  Only the
+// workgroup's FIRST unit has one more entry in front (slice zbeg - 1: its lead, or -- zbeg == 0 -- a dummy nobody reads), which keeps the ring rule
+// "step n reads stream entries n, n+1, n+2" (the centre of step n is entry n+1).  There is one step per stream entry behind that first one; a step is
+// live iff its centre is one of the unit's own slices, i.e. with the whole range per unit (zsplit == 1) a unit is exactly nz steps, all live.  A live
+// step whose centre is slice 0 (ni - 1) has no front (back) slice: the ring slot at that place holds a neighbouring unit's slice, and the kernel
+// leaves that slice's contraction chunks out.
+struct RollSched {
+    int z0;      // input slice of the unit's first stream entry
+    int fills;   // stream entries (= ring fills) of the unit
+    int steps;   // steps of the unit; step s is centred on input slice c0 + s
+    int c0;
+};
+__host__ __device__ inline RollSched roll_sched(int zbeg, int nz, int ni, bool first) {
+    const int lead = zbeg > 0 ? 1 : 0, trail = zbeg + nz < ni ? 1 : 0;
+    const int front = first ? 1 : lead;
+    RollSched s;
+    s.z0 = zbeg - front;
+    s.fills = front + nz + trail;
+    s.steps = first ? nz + trail : s.fills;
+    s.c0 = first ? zbeg : s.z0;
+    return s;
+}
+// what step `s` of a unit does: bit 0 = live, bit 1 = no front slice (its chunks are skipped), bit 2 = no back slice
+constexpr int ROLL_LIVE = 1, ROLL_NO_FRONT = 2, ROLL_NO_BACK = 4;
+__host__ __device__ inline int roll_step(const RollSched &sc, int s, int zbeg, int nz, int ni) {
+    const int c = sc.c0 + s;
+    if (c < zbeg || c >= zbeg + nz) return 0;
+    return ROLL_LIVE | (c == 0 ? ROLL_NO_FRONT : 0) | (c == ni - 1 ? ROLL_NO_BACK : 0);
+}
+// The contraction chunks of a step in K order, with those of an absent slice left out: `DZ::dz(c)` = window slice (0 front, 1 centre, 2 back) of
+// chunk c of NCH; M = ROLL_NO_FRONT / ROLL_NO_BACK bits of the step.  N chunks remain, at(i) is the i-th of them.
+template <class DZ, int NCH, int M>
+struct RollChunks {
+    static constexpr bool on(int c) { return !((M & ROLL_NO_FRONT) && DZ::dz(c) == 0) && !((M & ROLL_NO_BACK) && DZ::dz(c) == 2); }
+    static constexpr int count(int upto) {
+        int n = 0;
+        for (int c = 0; c < upto; ++c) n += on(c) ? 1 : 0;
+        return n;
+    }
+    static constexpr int N = count(NCH);
+    static constexpr int at(int i) {
+        for (int c = 0; c < NCH; ++c)
+            if (on(c) && count(c) == i) return c;
+        return NCH;
+    }
+};
+
+// window slice (0 front, 1 centre, 2 back) of contraction chunk c in each body's K order: which chunks a step without a front / back slice leaves out
+struct DzRoll {   // conv_roll plain form, conv_roll_s2: [dz][5]
+    static constexpr int dz(int c) { return c / 5; }
+};
+struct DzPair {   // conv_roll pair form: [dz][3 filter rows][2 halves]
+    static constexpr int dz(int c) { return c / 6; }
+};
+struct DzT {      // conv_roll_t: row phase 0 = chunks 0..2 (one per slice), row phase 1 = chunks 3..8 (two per slice)
+    static constexpr int dz(int c) { return c < 3 ? c : (c - 3) / 2; }
+};
+template <int NROW>
+struct DzT32 {    // conv_roll_t32: x phase 0 = [dz][NROW], x phase 1 = [dz][NROW][2]
+    static constexpr int dz(int c) { return c < 3 * NROW ? c / NROW : (c - 3 * NROW) / (2 * NROW); }
+};
+struct DzEfd {    // conv_roll_efd: [branch][dz][3]
+    static constexpr int dz(int c) { return (c % 9) / 3; }
+};
+
 constexpr int ROLL_CHUNKS = 15;        // 3 slices x 5 chunks of (2 in-slice taps x 16 channels)
 constexpr int ROLL_CHUNKS_PAIR = 18;   // pixel-pair form: 3 slices x 3 filter rows x 2 halves of (2 input columns x 16 channels)
 

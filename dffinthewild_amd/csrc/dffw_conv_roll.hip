@@ -12,12 +12,20 @@
 //   * the whole filter (27 taps x 16 channels x <= 16 output channels, hi + lo) lives in registers as 15 MFMA
 //     A-fragments per part: the inner loop issues only ds_read_b128 + v_mfma, no weight stream from L1/L2, no tap
 //     table (the contraction is fully unrolled, tap offsets are immediates, only the ring rotation is a register);
-//   * one barrier per slice.
+//   * one barrier per slice, and one step per output slice: a column of nz slices is nz ring fills, nz barriers and nz
+//     contractions (a workgroup's columns follow each other in one stream of real slices; no zero pages above or below
+//     the volume, no steps without an output -- the schedule is roll_sched / roll_step in dffw_conv_roll.h, replayed on
+//     the CPU by tools/roll_stream_model.cpp);
+//   * the first and the last slice of the volume have no neighbour on one side: their steps run a chunk list without that
+//     slice's chunks (RollChunks: straight-line code per case behind one wave-uniform branch, the operand read-ahead and
+//     its counted waits per list) -- a third of the step's MFMAs that only ever multiplied zeros.
 // K order: [dz][5 chunks of 32] with chunk k5 = in-slice taps 2*k5, 2*k5+1 (tap 9 = zero weights) x 16 channels, so
 // the slice of a chunk (= its ring slot) is wave-uniform.  Epilogue = conv_tile's (dffw_device.h).
+// All five bodies of this file and the two of dffw_conv_rollx.hip stream this way.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "dffw_conv_roll.h"
 #include "dffw_device.h"
@@ -68,8 +76,9 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
     using Unit = RollUnit;
     auto decode = [&](int u) { return roll_unit<TY, TX>(u, t, a.No); };
 
-    // ---- the slice stream.  The units of this workgroup form ONE stream of input slices: unit u contributes its
-    // nz+2 slices (one above, one below the outputs; zero pages outside the volume), then the next unit follows.  The
+    // ---- the slice stream.  The units of this workgroup form ONE stream of input slices: unit u contributes the real
+    // slices its outputs need -- its own nz and a halo slice where its range starts or ends inside the volume, no zero
+    // pages (roll_sched, dffw_conv_roll.h) -- then the next unit follows.  The
     // fill cursor runs RING-1 slices ahead of the window that is being contracted and simply keeps going across unit
     // boundaries, so only the first unit of a workgroup ever waits for a cold ring.
     // Per-lane fill state of the unit being fetched: piece p = wave*PPW + k of a slice covers 64 16-byte chunks (pixel,
@@ -81,8 +90,9 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
     int fu = ufirst, fq = 0, fslices = 0, fz0 = 0;        // fill cursor: unit, slice inside it, its slice count, first slice
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz0 = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz0 = fs.z0;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int p = wave * PPW + k;
@@ -159,7 +169,9 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
     static_assert(!LEAN || PARTS == 2, "the straight-line epilogue exists for split-bf16 storage");
     const bool lean_relu = a.relu == 1;
 
-    // Ring protocol.  Window n of the stream reads slices n, n+1, n+2 (ring slots n, n+1, n+2 mod RING).  The prologue
+    // Ring protocol.  Step n of the stream is centred on stream entry n+1 and reads entries n, n+1, n+2 (ring slots n, n+1, n+2
+    // mod RING) -- less the one the volume lacks when the centre is its first or last slice: that slot holds the neighbouring
+    // unit's slice (or, in front of the workgroup's first unit, a dummy), and the step leaves that slice's chunks out.  The prologue
     // queues slices 0 .. RING-2; iteration n queues slice n+RING-1 into the slot of slice n-1 (every wave left it
     // before the barrier of iteration n-1) -- ALWAYS, also past the end of the stream (zero page into a slot nobody
     // reads again), so the number of DMA pieces issued after any given slice is the same in every iteration.  vmcnt
@@ -208,7 +220,7 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
             sb[dz] = sl * SLOTB;
         }
     };
-    auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) {
+    auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) __attribute__((always_inline)) {
         if constexpr (PAIR) {
             // chunk c = (slice c/6, filter row (c%6)/2, half c%2): a compile-time offset from the lane's base
             const unsigned ad = lds0 + sb[c / 6] + pofs[0];
@@ -237,15 +249,19 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
             }
         }
     };
+    using DZ = std::conditional_t<PAIR, DzPair, DzRoll>;
+    // the first DEPTH chunks of a window that has its front slice (one that starts on the volume's first slice fetches its own: the first step of a unit)
+    auto prefetch = [&]() { static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { fetch(decltype(I)::value, x[decltype(I)::value]); }); };
     set_window();
-#pragma unroll
-    for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);   // (the prologue's slices have landed: barrier above)
+    prefetch();   // (the prologue's slices have landed: barrier above)
     StepTrace trc(a.trace, wave, lane, NWAVES);
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        const int64_t obase0 = (((int64_t)U.b * a.No + U.zbeg) * a.Ho + U.gy0) * a.Wo + U.gx0;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            const bool live = st < U.nz;   // windows starting on the unit's last two slices straddle two units: no output
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);
+        const int64_t obase0 = (((int64_t)U.b * a.No + sc.c0) * a.Ho + U.gy0) * a.Wo + U.gx0;
+        for (int st = 0; st < sc.steps; ++st) {
+            const int mode = roll_step(sc, st, U.zbeg, U.nz, a.Ni);
+            const bool live = mode & ROLL_LIVE;   // (a slice range that starts or ends inside the volume has a dead step on its halo slice)
             const int64_t obase = obase0 + (int64_t)st * a.Ho * a.Wo;
             const int64_t ubase = obase * (PARTS * a.Cout);
             trc.stamp(0);
@@ -274,38 +290,47 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
 #pragma unroll
             for (int j = 0; j < MTW; ++j) acc[j] = bias4;
             if (live && !(a.dbg & 2)) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + DEPTH < NCH) fetch(c + DEPTH, x[(c + DEPTH) % (DEPTH + 1)]);
-                    auto &xc = x[c % (DEPTH + 1)];
-                    const int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * RPC;   // compile-time after unrolling
-                    if (ahead == 2 * RPC && DEPTH == 2) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(2 * RPC));
-                    else if (ahead == RPC) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(RPC));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xc[0][0]));
-#pragma unroll
-                    for (int j = 0; j < MTW; ++j)
-#pragma unroll
-                        for (int pt = 0; pt < PARTS; ++pt)
-                            if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
-                    if constexpr (MTW == 1 && PARTS == 2) {
-                        // one operand tile per wave: the three products of a chunk would form one dependent chain (a dependent
-                        // 16x16x32 MFMA issues every ~26 cycles, an independent one every 16): the cross terms go to a second
-                        // accumulator, summed after the loop
-                        acc2 = mma<F16>(w[c][1], xc[0][0], acc2);
-                        acc[0] = mma<F16>(w[c][0], xc[0][0], acc[0]);
-                        acc2 = mma<F16>(w[c][0], xc[0][1], acc2);
-                    } else {
-                        if constexpr (PARTS == 2) {
-#pragma unroll
-                            for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][1], xc[j][0], acc[j]);
-#pragma unroll
-                            for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][0], xc[j][1], acc[j]);
+                // the chunks of the slices the window has (their first DEPTH are on their way: prefetch())
+                roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) {
+                    using CH = RollChunks<DZ, NCH, decltype(M)::value>;
+                    static_assert(CH::N >= DEPTH, "pipeline depth");
+                    // without a front slice the list starts behind the chunks prefetch() asked for: the same registers are requested again (DS
+                    // operations return in order: the later read is the one that stays)
+                    if constexpr (CH::at(0) != 0) static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { constexpr int c = CH::at(decltype(I)::value); fetch(c, x[decltype(I)::value]); });
+                    static_for<CH::N>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value, c = CH::at(i);
+                        if constexpr (i + DEPTH < CH::N) {
+                            constexpr int cn = CH::at(i + DEPTH);   // (a constant: the tap offsets must stay immediates)
+                            fetch(cn, x[(i + DEPTH) % (DEPTH + 1)]);
                         }
+                        auto &xc = x[i % (DEPTH + 1)];
+                        constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * RPC;
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(ahead));
 #pragma unroll
-                        for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][0], xc[j][0], acc[j]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                        for (int j = 0; j < MTW; ++j)
+#pragma unroll
+                            for (int pt = 0; pt < PARTS; ++pt)
+                                if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
+                        if constexpr (MTW == 1 && PARTS == 2) {
+                            // one operand tile per wave: the three products of a chunk would form one dependent chain (a dependent
+                            // 16x16x32 MFMA issues every ~26 cycles, an independent one every 16): the cross terms go to a second
+                            // accumulator, summed after the loop
+                            acc2 = mma<F16>(w[c][1], xc[0][0], acc2);
+                            acc[0] = mma<F16>(w[c][0], xc[0][0], acc[0]);
+                            acc2 = mma<F16>(w[c][0], xc[0][1], acc2);
+                        } else {
+                            if constexpr (PARTS == 2) {
+#pragma unroll
+                                for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][1], xc[j][0], acc[j]);
+#pragma unroll
+                                for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][0], xc[j][1], acc[j]);
+                            }
+#pragma unroll
+                            for (int j = 0; j < MTW; ++j) acc[j] = mma<F16>(w[c][0], xc[j][0], acc[j]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
                 if constexpr (MTW == 1 && PARTS == 2) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) acc[0][i] += acc2[i];
@@ -323,8 +348,7 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll(const ConvArgs a, const
             }
             sidx = (sidx + 1 == RING) ? 0 : sidx + 1;
             set_window();
-#pragma unroll
-            for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);   // the next window's first chunks (also behind the last step: the slots exist)
+            prefetch();   // the next window's first chunks (also behind the last step: the slots exist)
             trc.stamp(3);
             if (!live) {
                 trc.next();
@@ -451,8 +475,9 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll_t(const ConvArgs a, con
     int fu = ufirst, fq = 0, fslices = 0, fz0 = 0;
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz0 = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz0 = fs.z0;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int p = wave * PPW + k;
@@ -524,9 +549,11 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll_t(const ConvArgs a, con
     int sidx = 0;
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        const int64_t obase0 = (((int64_t)U.b * a.No + U.zbeg) * a.Ho + 2 * U.gy0) * a.Wo + 2 * U.gx0;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            const bool live = st < U.nz;
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);
+        const int64_t obase0 = (((int64_t)U.b * a.No + sc.c0) * a.Ho + 2 * U.gy0) * a.Wo + 2 * U.gx0;
+        for (int st = 0; st < sc.steps; ++st) {
+            const int mode = roll_step(sc, st, U.zbeg, U.nz, a.Ni);
+            const bool live = mode & ROLL_LIVE;
             const int64_t obase = obase0 + (int64_t)st * a.Ho * a.Wo;
             const int64_t ubase = obase * (PARTS * 8);
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -561,9 +588,8 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll_t(const ConvArgs a, con
                 }
                 constexpr int RPC = MTW * PARTS;
                 constexpr int DEPTH = 2;
-                short8 x[DEPTH + 1][MTW][PARTS];
                 // chunk c: c < 3: py = 0, slice c, input row y; c >= 3: py = 1, slice (c-3)/2, input row y + (c-3)%2
-                auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) {
+                auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) __attribute__((always_inline)) {
                     const int dz = c < 3 ? c : (c - 3) / 2;
                     const bool down = c >= 3 && ((c - 3) & 1);
 #pragma unroll
@@ -578,32 +604,38 @@ __global__ __launch_bounds__(NWAVES * 64) void conv_roll_t(const ConvArgs a, con
                         }
                     }
                 };
+                // the chunks of the slices the window has, operand fragments DEPTH chunks ahead of the MFMAs
+                roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) {
+                    using CH = RollChunks<DzT, NCH, decltype(M)::value>;
+                    static_assert(CH::N >= DEPTH, "pipeline depth");
+                    short8 x[DEPTH + 1][MTW][PARTS];
+                    static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { constexpr int c = CH::at(decltype(I)::value); fetch(c, x[decltype(I)::value]); });
+                    static_for<CH::N>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value, c = CH::at(i);
+                        if constexpr (i + DEPTH < CH::N) {
+                            constexpr int cn = CH::at(i + DEPTH);   // (a constant: the tap offsets must stay immediates)
+                            fetch(cn, x[(i + DEPTH) % (DEPTH + 1)]);
+                        }
+                        auto &xc = x[i % (DEPTH + 1)];
+                        constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * RPC;
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(ahead));
 #pragma unroll
-                for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);
+                        for (int j = 0; j < MTW; ++j)
 #pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + DEPTH < NCH) fetch(c + DEPTH, x[(c + DEPTH) % (DEPTH + 1)]);
-                    auto &xc = x[c % (DEPTH + 1)];
-                    const int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * RPC;
-                    if (ahead == 2 * RPC) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(2 * RPC));
-                    else if (ahead == RPC) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(RPC));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xc[0][0]));
+                            for (int pt = 0; pt < PARTS; ++pt)
+                                if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
+                        constexpr int py = c < 3 ? 0 : 1;
+                        if constexpr (PARTS == 2) {
 #pragma unroll
-                    for (int j = 0; j < MTW; ++j)
+                            for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][1], xc[j][0], acc[py][j]);
 #pragma unroll
-                        for (int pt = 0; pt < PARTS; ++pt)
-                            if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
-                    const int py = c < 3 ? 0 : 1;
-                    if constexpr (PARTS == 2) {
+                            for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][0], xc[j][1], acc[py][j]);
+                        }
 #pragma unroll
-                        for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][1], xc[j][0], acc[py][j]);
-#pragma unroll
-                        for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][0], xc[j][1], acc[py][j]);
-                    }
-#pragma unroll
-                    for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][0], xc[j][0], acc[py][j]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                        for (int j = 0; j < MTW; ++j) acc[py][j] = mma<F16>(w[c][0], xc[j][0], acc[py][j]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
             }
 
             asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(INFLIGHT) : "memory");
@@ -703,8 +735,9 @@ __global__ __launch_bounds__(256) void conv_roll_t32(const ConvArgs a, const Rol
     int fu = ufirst, fq = 0, fslices = 0, fz0 = 0;
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz0 = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz0 = fs.z0;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int p = wave * PPW + k;
@@ -777,9 +810,11 @@ __global__ __launch_bounds__(256) void conv_roll_t32(const ConvArgs a, const Rol
     int sidx = 0;
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        const int64_t obase0 = (((int64_t)U.b * a.No + U.zbeg) * a.Ho + 2 * U.gy0) * a.Wo + 2 * U.gx0;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            const bool live = st < U.nz;
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);
+        const int64_t obase0 = (((int64_t)U.b * a.No + sc.c0) * a.Ho + 2 * U.gy0) * a.Wo + 2 * U.gx0;
+        for (int st = 0; st < sc.steps; ++st) {
+            const int mode = roll_step(sc, st, U.zbeg, U.nz, a.Ni);
+            const bool live = mode & ROLL_LIVE;
             const int64_t obase = obase0 + (int64_t)st * a.Ho * a.Wo;
             const int64_t ubase = obase * (PARTS * 16);
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -814,10 +849,9 @@ __global__ __launch_bounds__(256) void conv_roll_t32(const ConvArgs a, const Rol
                 }
                 constexpr int RPC = MTW * PARTS;
                 constexpr int DEPTH = 2;
-                short8 x[DEPTH + 1][MTW][PARTS];
                 // chunk c < NCH0: x phase 0, (slice d, row tap rt) = (c / NROW, c % NROW), input column x;
                 // c >= NCH0: x phase 1, e = c - NCH0: (d, rt, column tap ct) = (e / (2*NROW), (e / 2) % NROW, e % 2): ct = 0 -> column x, 1 -> x+1
-                auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) {
+                auto fetch = [&](int c, short8 (&dst)[MTW][PARTS]) __attribute__((always_inline)) {
                     const int e = c - NCH0;
                     const int dz = c < NCH0 ? c / NROW : e / (2 * NROW);
                     const int rt = c < NCH0 ? c % NROW : (e / 2) % NROW;
@@ -831,32 +865,38 @@ __global__ __launch_bounds__(256) void conv_roll_t32(const ConvArgs a, const Rol
                         if constexpr (PARTS == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[j][1]) : "v"(ad), "n"(PLANEB));
                     }
                 };
+                // the chunks of the slices the window has, operand fragments DEPTH chunks ahead of the MFMAs
+                roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) {
+                    using CH = RollChunks<DzT32<NROW>, NCH, decltype(M)::value>;
+                    static_assert(CH::N >= DEPTH, "pipeline depth");
+                    short8 x[DEPTH + 1][MTW][PARTS];
+                    static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { constexpr int c = CH::at(decltype(I)::value); fetch(c, x[decltype(I)::value]); });
+                    static_for<CH::N>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value, c = CH::at(i);
+                        if constexpr (i + DEPTH < CH::N) {
+                            constexpr int cn = CH::at(i + DEPTH);   // (a constant: the tap offsets must stay immediates)
+                            fetch(cn, x[(i + DEPTH) % (DEPTH + 1)]);
+                        }
+                        auto &xc = x[i % (DEPTH + 1)];
+                        constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * RPC;
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(ahead));
 #pragma unroll
-                for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);
+                        for (int j = 0; j < MTW; ++j)
 #pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + DEPTH < NCH) fetch(c + DEPTH, x[(c + DEPTH) % (DEPTH + 1)]);
-                    auto &xc = x[c % (DEPTH + 1)];
-                    const int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * RPC;
-                    if (ahead == 2 * RPC) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(2 * RPC));
-                    else if (ahead == RPC) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0][0]) : "n"(RPC));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xc[0][0]));
+                            for (int pt = 0; pt < PARTS; ++pt)
+                                if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
+                        constexpr int px = c < NCH0 ? 0 : 1;
+                        if constexpr (PARTS == 2) {
 #pragma unroll
-                    for (int j = 0; j < MTW; ++j)
+                            for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][1], xc[j][0], acc[px][j]);
 #pragma unroll
-                        for (int pt = 0; pt < PARTS; ++pt)
-                            if (j + pt) asm volatile("" : "+v"(xc[j][pt]));
-                    const int px = c < NCH0 ? 0 : 1;
-                    if constexpr (PARTS == 2) {
+                            for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][0], xc[j][1], acc[px][j]);
+                        }
 #pragma unroll
-                        for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][1], xc[j][0], acc[px][j]);
-#pragma unroll
-                        for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][0], xc[j][1], acc[px][j]);
-                    }
-#pragma unroll
-                    for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][0], xc[j][0], acc[px][j]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                        for (int j = 0; j < MTW; ++j) acc[px][j] = mma<F16>(w[c][0], xc[j][0], acc[px][j]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
             }
 
             asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(INFLIGHT) : "memory");
@@ -952,8 +992,9 @@ __global__ __launch_bounds__(256) void conv_roll_efd(const ConvArgs a, const Rol
     int fu = ufirst, fq = 0, fslices = 0, fz0 = 0;
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz0 = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz0 = fs.z0;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int p = wave * PPW + k;
@@ -1045,9 +1086,11 @@ __global__ __launch_bounds__(256) void conv_roll_efd(const ConvArgs a, const Rol
     int sidx = 0;
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        const int64_t obase0 = (((int64_t)U.b * a.No + U.zbeg) * a.Ho + U.gy0) * a.Wo + U.gx0;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            const bool live = st < U.nz;
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);
+        const int64_t obase0 = (((int64_t)U.b * a.No + sc.c0) * a.Ho + U.gy0) * a.Wo + U.gx0;
+        for (int st = 0; st < sc.steps; ++st) {
+            const int mode = roll_step(sc, st, U.zbeg, U.nz, a.Ni);
+            const bool live = mode & ROLL_LIVE;   // (a slice range that starts or ends inside the volume has a dead step on its halo slice)
             const int64_t obase = obase0 + (int64_t)st * a.Ho * a.Wo;
             const int64_t ubase = obase * (PARTS * 16);
             if (!(a.dbg & 1)) issue_next();
@@ -1062,31 +1105,36 @@ __global__ __launch_bounds__(256) void conv_roll_efd(const ConvArgs a, const Rol
                     sb[dz] = sl * SLOTB;
                 }
                 constexpr int DEPTH = 2;
-                short8 x[DEPTH + 1][PARTS];
-                auto fetch = [&](int c, short8 (&dst)[PARTS]) {
+                auto fetch = [&](int c, short8 (&dst)[PARTS]) __attribute__((always_inline)) {
                     const int cc = c % 9, dz = cc / 3, k3 = cc % 3;
                     const unsigned ad = lds0 + sb[dz] + (c < 9 ? baseX + tapX[k3] : baseP + tapP[k3]);
                     asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(ad));
                     if constexpr (PARTS == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(ad), "n"(PLANEB));
                 };
-#pragma unroll
-                for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + DEPTH < NCH) fetch(c + DEPTH, x[(c + DEPTH) % (DEPTH + 1)]);
-                    auto &xc = x[c % (DEPTH + 1)];
-                    const int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * PARTS;
-                    if (ahead == 2 * PARTS) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(2 * PARTS));
-                    else if (ahead == PARTS) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(PARTS));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xc[0]));
-                    if constexpr (PARTS == 2) {
-                        asm volatile("" : "+v"(xc[1]));
-                        acc = mma<F16>(w[c][1], xc[0], acc);
-                        acc = mma<F16>(w[c][0], xc[1], acc);
-                    }
-                    acc = mma<F16>(w[c][0], xc[0], acc);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                // the chunks of the slices the window has, operand fragments DEPTH chunks ahead of the MFMAs
+                roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) {
+                    using CH = RollChunks<DzEfd, NCH, decltype(M)::value>;
+                    static_assert(CH::N >= DEPTH, "pipeline depth");
+                    short8 x[DEPTH + 1][PARTS];
+                    static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { constexpr int c = CH::at(decltype(I)::value); fetch(c, x[decltype(I)::value]); });
+                    static_for<CH::N>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value, c = CH::at(i);
+                        if constexpr (i + DEPTH < CH::N) {
+                            constexpr int cn = CH::at(i + DEPTH);   // (a constant: the tap offsets must stay immediates)
+                            fetch(cn, x[(i + DEPTH) % (DEPTH + 1)]);
+                        }
+                        auto &xc = x[i % (DEPTH + 1)];
+                        constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * PARTS;
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(ahead));
+                        if constexpr (PARTS == 2) {
+                            asm volatile("" : "+v"(xc[1]));
+                            acc = mma<F16>(w[c][1], xc[0], acc);
+                            acc = mma<F16>(w[c][0], xc[1], acc);
+                        }
+                        acc = mma<F16>(w[c][0], xc[0], acc);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
             }
             asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(INFLIGHT) : "memory");
             sidx = (sidx + 1 == RING) ? 0 : sidx + 1;
@@ -1165,10 +1213,12 @@ __global__ __launch_bounds__(NT * KH == 4 ? 512 : 256) void conv_roll_s2(const C
     const int xslice = a.Hi * a.Wi * rec;
     const uint16_t *fsrc[PPW];
     bool fok[PPW];
-    int fu = ufirst, fq = 0;
-    const int fslices = a.No + 2;
+    int fu = ufirst, fq = 0, fslices = 0, fz0 = 0;   // (a unit is the whole slice range of its column: no zsplit here)
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
+        const RollSched fs = roll_sched(0, a.No, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz0 = fs.z0;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int p = wave * PPW + k;
@@ -1184,7 +1234,7 @@ __global__ __launch_bounds__(NT * KH == 4 ? 512 : 256) void conv_roll_s2(const C
     setup_fill();
     int fslot = 0;
     auto issue_next = [&]() {
-        const int iz = fq - 1;
+        const int iz = fz0 + fq;
         const bool zin = (unsigned)iz < (unsigned)a.Ni && fu < uend;
         unsigned char *slot = smem + fslot * SLOTB;
 #pragma unroll
@@ -1253,9 +1303,11 @@ __global__ __launch_bounds__(NT * KH == 4 ? 512 : 256) void conv_roll_s2(const C
     int sidx = 0, parity = 0;
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        const int64_t obase0 = (((int64_t)U.b * a.No) * a.Ho + U.gy0) * a.Wo + U.gx0;
-        for (int st = 0; st < a.No + 2; ++st) {
-            const bool live = st < a.No;
+        const RollSched sc = roll_sched(0, a.No, a.Ni, cu == ufirst);
+        const int64_t obase0 = (((int64_t)U.b * a.No + sc.c0) * a.Ho + U.gy0) * a.Wo + U.gx0;
+        for (int st = 0; st < sc.steps; ++st) {
+            const int mode = roll_step(sc, st, 0, a.No, a.Ni);
+            const bool live = mode & ROLL_LIVE;
             const int64_t obase = obase0 + (int64_t)st * a.Ho * a.Wo;
             const int64_t ubase = obase * (PARTS * Cout);
             if (!(a.dbg & 1)) issue_next();
@@ -1270,30 +1322,35 @@ __global__ __launch_bounds__(NT * KH == 4 ? 512 : 256) void conv_roll_s2(const C
                     sb[dz] = sl * SLOTB;
                 }
                 constexpr int DEPTH = 2;
-                short8 x[DEPTH + 1][PARTS];
-                auto fetch = [&](int c, short8 (&dst)[PARTS]) {
+                auto fetch = [&](int c, short8 (&dst)[PARTS]) __attribute__((always_inline)) {
                     const unsigned ad = lds0 + sb[c / 5] + base + tapo[c % 5];
                     asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(ad));
                     if constexpr (PARTS == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(ad), "n"(PLANEB));
                 };
-#pragma unroll
-                for (int c = 0; c < DEPTH; ++c) fetch(c, x[c]);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + DEPTH < NCH) fetch(c + DEPTH, x[(c + DEPTH) % (DEPTH + 1)]);
-                    auto &xc = x[c % (DEPTH + 1)];
-                    const int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * PARTS;
-                    if (ahead == 2 * PARTS) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(2 * PARTS));
-                    else if (ahead == PARTS) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(PARTS));
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xc[0]));
-                    if constexpr (PARTS == 2) {
-                        asm volatile("" : "+v"(xc[1]));
-                        acc = mma<F16>(w[c][1], xc[0], acc);
-                        acc = mma<F16>(w[c][0], xc[1], acc);
-                    }
-                    acc = mma<F16>(w[c][0], xc[0], acc);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                // the chunks of the slices the window has, operand fragments DEPTH chunks ahead of the MFMAs
+                roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) {
+                    using CH = RollChunks<DzRoll, NCH, decltype(M)::value>;
+                    static_assert(CH::N >= DEPTH, "pipeline depth");
+                    short8 x[DEPTH + 1][PARTS];
+                    static_for<DEPTH>([&](auto I) __attribute__((always_inline)) { constexpr int c = CH::at(decltype(I)::value); fetch(c, x[decltype(I)::value]); });
+                    static_for<CH::N>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value, c = CH::at(i);
+                        if constexpr (i + DEPTH < CH::N) {
+                            constexpr int cn = CH::at(i + DEPTH);   // (a constant: the tap offsets must stay immediates)
+                            fetch(cn, x[(i + DEPTH) % (DEPTH + 1)]);
+                        }
+                        auto &xc = x[i % (DEPTH + 1)];
+                        constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * PARTS;
+                        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xc[0]) : "n"(ahead));
+                        if constexpr (PARTS == 2) {
+                            asm volatile("" : "+v"(xc[1]));
+                            acc = mma<F16>(w[c][1], xc[0], acc);
+                            acc = mma<F16>(w[c][0], xc[1], acc);
+                        }
+                        acc = mma<F16>(w[c][0], xc[0], acc);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
             }
             if constexpr (KH == 2) {   // the odd channel half hands its partial tile to its partner (the wave below it)
                 const unsigned xo = lds0 + RING * SLOTB + (parity * (NWAVES / 2) + (wave >> 1)) * 1024 + lane * 16;

@@ -12,6 +12,12 @@
 //     hardware range check writes their zeros -- no 64-bit pointer per piece, no zero page, no per-piece select, one M0 write per piece;
 //   * the step body is instantiated per (live(n), live(n-1), live(n-2)) so the interleaved code is straight-line (a counted
 //     s_waitcnt tied to fragment registers must not sit behind a branch) and the vmcnt window is exact;
+//   * the stream holds real slices only and has one step per output slice (roll_sched / roll_step, dffw_conv_roll.h; replayed on the CPU by
+//     tools/roll_stream_model.cpp): a column of nz slices is nz fills, nz barriers, nz contractions, and the pending epilogue of a column's last
+//     slice runs inside the first step of the workgroup's next column (the stream's very last one in a drain step of its own).  The steps on the
+//     volume's first and last slice have no front / back slice -- the ring slot there holds the neighbouring column's -- and run a chunk list
+//     without that slice's chunks (RollChunks: a live step is instantiated per absent-slice case as well); the side work that finds no chunk gap
+//     in a shorter list follows the list;
 //   * LDS slice image = [tensor / channel octet][part][pixel] planes of 16-byte entries (the two 8-channel inputs of a virtual concat
 //     are different tensors, and a DMA piece has ONE descriptor), rows stored even columns first; a wave's operand tile is rows w and
 //     w + 4 of the 8-row column: their 72-entry distance is 8 mod 16, so the 16 lanes of a ds_read_b128 row group cover 16 distinct
@@ -80,8 +86,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int fu = ufirst, fq = 0, fslices = 0, fz = 0;      // fill cursor: unit, slice inside it, its slice count, input slice index
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz = fs.z0;
         fbase = tbase + ((int64_t)c.b * a.Ni * a.Hi * a.Wi + (int64_t)(c.gy0 - 1) * a.Wi + (c.gx0 - 1)) * recb;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
@@ -145,9 +152,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     StepTrace trc(a.trace, wave, lane, NW);
 
     // One step of the stream.  LIVE: this window produces an output slice; PEND: the previous one did (its epilogue runs now);
-    // PEND2: the one before that did (its store is still inside the vmcnt window).
-    auto step = [&](auto LIVE_, auto PEND_, auto PEND2_, char *optr) {
+    // PEND2: the one before that did (its store is still inside the vmcnt window); M: the window has no front / back slice (ROLL_NO_FRONT / ROLL_NO_BACK:
+    // the centre is the volume's first / last slice) -- that slice's chunks are left out
+    auto step = [&](auto LIVE_, auto PEND_, auto PEND2_, auto M_, char *optr) __attribute__((always_inline)) {
         constexpr bool LIVE = decltype(LIVE_)::value, PEND = decltype(PEND_)::value, PEND2 = decltype(PEND2_)::value;
+        using CH = RollChunks<DzPair, NCH, decltype(M_)::value>;
         trc.stamp(0);
         // the pending step's value: its three accumulators are complete (a barrier ago)
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
@@ -213,33 +222,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             trc.stamp(1);
             constexpr int DEPTH = 2, NB = DEPTH + 1;
             short8 x[NB][2];
-            auto fetch = [](auto C, short8 (&xx)[NB][2], const unsigned (&adr)[3]) {
-                constexpr int c = decltype(C)::value;
+            // the I-th chunk of the step's list (chunk CH::at(I)) into buffer I % NB
+            auto fetch = [](auto I, short8 (&xx)[NB][2], const unsigned (&adr)[3]) {
+                constexpr int i = decltype(I)::value, c = CH::at(i);
                 constexpr int imm = (((c % 6) / 2) * ROWE + (c % 2)) * 16;
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[c % NB][0]) : "v"(adr[c / 6]), "n"(imm));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[c % NB][1]) : "v"(adr[c / 6]), "n"(imm + FX * 16));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[i % NB][0]) : "v"(adr[c / 6]), "n"(imm));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[i % NB][1]) : "v"(adr[c / 6]), "n"(imm + FX * 16));
             };
-            if constexpr (!(ABL & 1)) static_for<DEPTH>([&](auto C) { fetch(C, x, ad); });
+            static_assert(CH::N >= DEPTH, "pipeline depth");
+            if constexpr (!(ABL & 1)) static_for<DEPTH>([&](auto I) { fetch(I, x, ad); });
             else static_for<NB>([&](auto C) { x[decltype(C)::value][0] = w[0][0]; x[decltype(C)::value][1] = w[1][1]; });
             f32x4 n0 = bias4, n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
-            static_for<NCH>([&](auto C) {
-                constexpr int c = decltype(C)::value;
-                if constexpr (c + DEPTH < NCH && !(ABL & 1)) fetch(std::integral_constant<int, c + DEPTH>{}, x, ad);
-                constexpr int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * 2;
-                if constexpr (!(ABL & 1)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x[c % NB][0]), "+v"(x[c % NB][1]) : "n"(ahead));
-                else asm volatile("" : "+v"(x[c % NB][0]), "+v"(x[c % NB][1]));
+            static_for<CH::N>([&](auto I) {
+                constexpr int i = decltype(I)::value, c = CH::at(i);
+                if constexpr (i + DEPTH < CH::N && !(ABL & 1)) fetch(std::integral_constant<int, i + DEPTH>{}, x, ad);
+                constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * 2;
+                if constexpr (!(ABL & 1)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x[i % NB][0]), "+v"(x[i % NB][1]) : "n"(ahead));
+                else asm volatile("" : "+v"(x[i % NB][0]), "+v"(x[i % NB][1]));
                 if constexpr (!(ABL & 2)) {
-                    n0 = mma<false>(w[c][0], x[c % NB][0], n0);
-                    n1 = mma<false>(w[c][1], x[c % NB][0], n1);
-                    n2 = mma<false>(w[c][0], x[c % NB][1], n2);
+                    n0 = mma<false>(w[c][0], x[i % NB][0], n0);
+                    n1 = mma<false>(w[c][1], x[i % NB][0], n1);
+                    n2 = mma<false>(w[c][0], x[i % NB][1], n2);
                 } else {
-                    asm volatile("" ::"v"(x[c % NB][0]), "v"(x[c % NB][1]), "v"(w[c][0]), "v"(w[c][1]));
+                    asm volatile("" ::"v"(x[i % NB][0]), "v"(x[i % NB][1]), "v"(w[c][0]), "v"(w[c][1]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (c >= 1 && c <= 9) {
-                    side(std::integral_constant<int, c - 1>{});
+                if constexpr (i >= 1 && i <= 9) {
+                    side(std::integral_constant<int, i - 1>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
+            });
+            // (a volume of one slice: six chunks have five gaps -- the rest of the side work follows them)
+            static_for<9>([&](auto S) {
+                if constexpr (decltype(S)::value >= CH::N - 1) side(S);
             });
             acc0 = n0;
             acc1 = n1;
@@ -262,33 +277,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     int hist = 0;   // bit 0: the previous step was live, bit 1: the one before
-    auto dispatch = [&](bool live, char *optr) {
+    auto dispatch = [&](int mode, char *optr) __attribute__((always_inline)) {   // mode: roll_step()
         using T = std::true_type;
         using F = std::false_type;
-        switch ((live ? 4 : 0) | hist) {
-            case 0: step(F{}, F{}, F{}, optr); break;
-            case 1: step(F{}, T{}, F{}, optr); break;
-            case 2: step(F{}, F{}, T{}, optr); break;
-            case 3: step(F{}, T{}, T{}, optr); break;
-            case 4: step(T{}, F{}, F{}, optr); break;
-            case 5: step(T{}, T{}, F{}, optr); break;
-            case 6: step(T{}, F{}, T{}, optr); break;
-            default: step(T{}, T{}, T{}, optr); break;
-        }
+        auto with_hist = [&](auto LIVE, auto M) __attribute__((always_inline)) {
+            switch (hist) {
+                case 0: step(LIVE, F{}, F{}, M, optr); break;
+                case 1: step(LIVE, T{}, F{}, M, optr); break;
+                case 2: step(LIVE, F{}, T{}, M, optr); break;
+                default: step(LIVE, T{}, T{}, M, optr); break;
+            }
+        };
+        const bool live = mode & ROLL_LIVE;
+        if (live) roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) { with_hist(T{}, M); });
+        else with_hist(F{}, std::integral_constant<int, 0>{});
         hist = ((hist << 1) & 2) | (live ? 1 : 0);
     };
 
     const int64_t ostride = (int64_t)a.Ho * a.Wo * 32;   // bytes per output slice
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        char *optr = reinterpret_cast<char *>(a.out) + ((((int64_t)U.b * a.No + U.zbeg) * a.Ho + U.gy0) * a.Wo + U.gx0) * 32;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            dispatch(st < U.nz, optr);   // windows starting on the unit's last two slices straddle two units: no output
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);   // one step per stream slice: nz of them for a whole slice range, all live
+        char *optr = reinterpret_cast<char *>(a.out) + ((((int64_t)U.b * a.No + sc.c0) * a.Ho + U.gy0) * a.Wo + U.gx0) * 32;
+        for (int st = 0; st < sc.steps; ++st) {
+            dispatch(roll_step(sc, st, U.zbeg, U.nz, a.Ni), optr);   // (the pending epilogue carries its own output base across the unit boundary: pptr)
             optr += ostride;
         }
     }
-    // the last live step's epilogue is still pending (a unit ends with two dead steps, which have run it) -- and the slices queued
-    // past the end of the stream are still in flight: a wave must not retire before its LDS-DMA has landed
+    // the drain: the epilogue of the stream's last live step is still pending -- one step without a window runs it
+    if (hist & 1) dispatch(0, nullptr);
+    // the slices queued past the end of the stream are still in flight: a wave must not retire before its LDS-DMA has landed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -353,8 +371,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int fu = ufirst, fq = 0, fslices = 0, fz = 0;
     auto setup_fill = [&]() {
         const Unit c = decode(fu);
-        fslices = c.nz + 2;
-        fz = c.zbeg - 1;
+        const RollSched fs = roll_sched(c.zbeg, c.nz, a.Ni, fu == ufirst);
+        fslices = fs.fills;
+        fz = fs.z0;
         fbase = tbase + ((int64_t)c.b * a.Ni * a.Hi * a.Wi + (int64_t)(c.gy0 - 1) * a.Wi + (c.gx0 - 1)) * recb;
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
@@ -421,8 +440,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     f32x4 mine = {0.f, 0.f, 0.f, 0.f};   // this wave's own partial of the tile it finishes (pending step)
     char *pptr = nullptr;
 
-    auto step = [&](auto LIVE_, auto PEND_, auto PEND2_, char *optr) {
-        constexpr bool LIVE = decltype(LIVE_)::value, PEND = decltype(PEND_)::value, PEND2 = decltype(PEND2_)::value;
+    auto step = [&](auto LIVE_, auto PEND_, auto M_, char *optr) __attribute__((always_inline)) {   // M: the window's absent slices, as in conv_rollx_pair
+        constexpr bool LIVE = decltype(LIVE_)::value, PEND = decltype(PEND_)::value;
+        using CH = RollChunks<DzRoll, NCH, decltype(M_)::value>;
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
         uint32_t h01 = 0, h23 = 0, l01 = 0, l23 = 0;
         f32x4 theirs = {0.f, 0.f, 0.f, 0.f};
@@ -480,15 +500,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             sb[2] = (sb[1] + SLOTB == RING * SLOTB) ? 0 : sb[1] + SLOTB;
             constexpr int DEPTH = 2, NB = DEPTH + 1;
             short8 x[NB][2][2];   // [buffer][tile][part]
-            auto fetch = [](auto C, short8 (&xx)[NB][2][2], const unsigned (&ao)[5], const int (&sbb)[3]) {
-                constexpr int c = decltype(C)::value;
+            // the I-th chunk of the step's list (chunk CH::at(I)) into buffer I % NB
+            auto fetch = [](auto I, short8 (&xx)[NB][2][2], const unsigned (&ao)[5], const int (&sbb)[3]) {
+                constexpr int i = decltype(I)::value, c = CH::at(i);
                 const unsigned ad = ao[c % 5] + sbb[c / 5];
-                asm volatile("ds_read_b128 %0, %1" : "=v"(xx[c % NB][0][0]) : "v"(ad));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[c % NB][0][1]) : "v"(ad), "n"(PARTB));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[c % NB][1][0]) : "v"(ad), "n"(ROWB));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[c % NB][1][1]) : "v"(ad), "n"(ROWB + PARTB));
+                asm volatile("ds_read_b128 %0, %1" : "=v"(xx[i % NB][0][0]) : "v"(ad));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[i % NB][0][1]) : "v"(ad), "n"(PARTB));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[i % NB][1][0]) : "v"(ad), "n"(ROWB));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xx[i % NB][1][1]) : "v"(ad), "n"(ROWB + PARTB));
             };
-            static_for<DEPTH>([&](auto C) { fetch(C, x, aoff, sb); });
+            static_assert(CH::N >= DEPTH, "pipeline depth");
+            static_for<DEPTH>([&](auto I) { fetch(I, x, aoff, sb); });
             f32x4 n[2][3];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -496,23 +518,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 n[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
                 n[j][2] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            static_for<NCH>([&](auto C) {
-                constexpr int c = decltype(C)::value;
-                if constexpr (c + DEPTH < NCH) fetch(std::integral_constant<int, c + DEPTH>{}, x, aoff, sb);
-                constexpr int ahead = (NCH - 1 - c < DEPTH ? NCH - 1 - c : DEPTH) * 4;
-                asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x[c % NB][0][0]), "+v"(x[c % NB][0][1]), "+v"(x[c % NB][1][0]), "+v"(x[c % NB][1][1]) : "n"(ahead));
-                if constexpr (PEND && c == 0) asm volatile("" : "+v"(theirs));   // older than chunk 0's reads: landed
+            static_for<CH::N>([&](auto I) {
+                constexpr int i = decltype(I)::value, c = CH::at(i);
+                if constexpr (i + DEPTH < CH::N) fetch(std::integral_constant<int, i + DEPTH>{}, x, aoff, sb);
+                constexpr int ahead = (CH::N - 1 - i < DEPTH ? CH::N - 1 - i : DEPTH) * 4;
+                asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x[i % NB][0][0]), "+v"(x[i % NB][0][1]), "+v"(x[i % NB][1][0]), "+v"(x[i % NB][1][1]) : "n"(ahead));
+                if constexpr (PEND && i == 0) asm volatile("" : "+v"(theirs));   // older than the first chunk's reads: landed
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    n[j][0] = mma<false>(w[c][0], x[c % NB][j][0], n[j][0]);
-                    n[j][1] = mma<false>(w[c][1], x[c % NB][j][0], n[j][1]);
-                    n[j][2] = mma<false>(w[c][0], x[c % NB][j][1], n[j][2]);
+                    n[j][0] = mma<false>(w[c][0], x[i % NB][j][0], n[j][0]);
+                    n[j][1] = mma<false>(w[c][1], x[i % NB][j][0], n[j][1]);
+                    n[j][2] = mma<false>(w[c][0], x[i % NB][j][1], n[j][2]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (c >= 1 && c <= 10) {
-                    side(std::integral_constant<int, c - 1>{});
+                if constexpr (i >= 1 && i <= 10) {
+                    side(std::integral_constant<int, i - 1>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
+            });
+            // (a window without its front or back slice has ten chunks, one of one slice five: the rest of the side work follows them)
+            static_for<10>([&](auto S) {
+                if constexpr (decltype(S)::value >= CH::N - 1) side(S);
             });
             // hand the partner its row's partial, keep mine
             f32x4 give;
@@ -529,7 +555,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         constexpr int INFLIGHT = PPW + (PEND ? 1 : 0);   // ring of 5: the slice queued in the PREVIOUS step is the next window's last one
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(INFLIGHT) : "memory");
-        (void)PEND2;
         sidxb = (sidxb + SLOTB == RING * SLOTB) ? 0 : sidxb + SLOTB;
         xpar ^= 1;
         advance_fill();
@@ -537,27 +562,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     int hist = 0;
-    auto dispatch = [&](bool live, char *optr) {
+    auto dispatch = [&](int mode, char *optr) __attribute__((always_inline)) {   // mode: roll_step()
         using T = std::true_type;
         using F = std::false_type;
-        switch ((live ? 2 : 0) | (hist & 1)) {
-            case 0: step(F{}, F{}, F{}, optr); break;
-            case 1: step(F{}, T{}, F{}, optr); break;
-            case 2: step(T{}, F{}, F{}, optr); break;
-            default: step(T{}, T{}, F{}, optr); break;
-        }
+        auto with_hist = [&](auto LIVE, auto M) __attribute__((always_inline)) {
+            if (hist & 1) step(LIVE, T{}, M, optr);
+            else step(LIVE, F{}, M, optr);
+        };
+        const bool live = mode & ROLL_LIVE;
+        if (live) roll_mode_switch(mode, [&](auto M) __attribute__((always_inline)) { with_hist(T{}, M); });
+        else with_hist(F{}, std::integral_constant<int, 0>{});
         hist = live ? 1 : 0;
     };
 
     const int64_t ostride = (int64_t)a.Ho * a.Wo * 64;   // bytes per output slice (16 channels, hi + lo)
     for (int cu = ufirst; cu < uend; cu += wgs_per_xcd) {
         const Unit U = decode(cu);
-        char *optr = reinterpret_cast<char *>(a.out) + ((((int64_t)U.b * a.No + U.zbeg) * a.Ho + U.gy0) * a.Wo + U.gx0) * 64;
-        for (int st = 0; st < U.nz + 2; ++st) {
-            dispatch(st < U.nz, optr);
+        const RollSched sc = roll_sched(U.zbeg, U.nz, a.Ni, cu == ufirst);
+        char *optr = reinterpret_cast<char *>(a.out) + ((((int64_t)U.b * a.No + sc.c0) * a.Ho + U.gy0) * a.Wo + U.gx0) * 64;
+        for (int st = 0; st < sc.steps; ++st) {
+            dispatch(roll_step(sc, st, U.zbeg, U.nz, a.Ni), optr);
             optr += ostride;
         }
     }
+    if (hist & 1) dispatch(0, nullptr);   // the drain: the last live step's epilogue (and its partner's partial) is still pending
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "dffw_conv_roll.h"
 
@@ -115,6 +116,17 @@ __device__ __forceinline__ RollUnit roll_unit(int u, const RollArgs &t, int no) 
     c.zbeg = zp * no / t.zsplit;
     c.nz = (zp + 1) * no / t.zsplit - c.zbeg;
     return c;
+}
+
+// f(M) for the step's absent-slice bits M as a compile-time constant: the step's chunk list is straight-line code behind one wave-uniform branch
+template <class F>
+__device__ __forceinline__ void roll_mode_switch(int mode, F &&f) {
+    switch (mode & (ROLL_NO_FRONT | ROLL_NO_BACK)) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case ROLL_NO_FRONT: f(std::integral_constant<int, ROLL_NO_FRONT>{}); break;
+        case ROLL_NO_BACK: f(std::integral_constant<int, ROLL_NO_BACK>{}); break;
+        default: f(std::integral_constant<int, ROLL_NO_FRONT | ROLL_NO_BACK>{}); break;   // a volume of one slice
+    }
 }
 
 }  // namespace dffw

@@ -404,15 +404,7 @@ static Act pyramid(Run &r, const std::string &S, const Act &v3) {
     ConvOpt rl; rl.relu = 1;
     Act p8, p16, p32;
     if (v3.H % 8 == 0 && v3.W % 8 == 0 && !r.sw.on(SW_NO_POOL3)) {   // one pass over v3 for the three pyramid scales (pool3_kernel)
-        p8 = r.act(v3.B, v3.N, v3.H / 2, v3.W / 2, v3.C);
-        p16 = r.act(v3.B, v3.N, v3.H / 4, v3.W / 4, v3.C);
-        p32 = r.act(v3.B, v3.N, v3.H / 8, v3.W / 8, v3.C);
-        if (r.ok() && !r.dry) {
-            char kn[48];
-            snprintf(kn, sizeof kn, "dffw::pool3_kernel<%d>", r.e->prec);
-            r.launch_unnamed(kn, "avgpool (1,2,2)+(1,4,4)+(1,8,8)", "", 0.0, (double)(v3.pixels() + p8.pixels() + p16.pixels() + p32.pixels()) * v3.C * r.elem_bytes(), "pool3", 0,
-                             [&](unsigned long long *) { return launch_pool3(r.e->prec, v3.p, p8.p, p16.p, p32.p, v3.B, v3.N, v3.H, v3.W, v3.C, r.s); });
-        }
+        r.pool3(v3, p8, p16, p32);
     } else {
         p8 = r.pool(v3, 1, 2);
         p16 = r.pool(v3, 1, 4);

@@ -502,7 +502,8 @@ __global__ __launch_bounds__(256) void pool_kernel(const uint16_t *__restrict__ 
 // pool3_kernel: the pyramid's three average pools (1,2,2), (1,4,4), (1,8,8) of the same volume (hourglassup.forward, DEN.py:212-216) in ONE pass: as three
 // launches the 32-channel volume was read three times (0.17 GB each at batch 32).  Work item = (8 x 8 block, channel octet); its 8 lanes hold one block row
 // each (8 pixels x 8 channels, joined to fp32 in registers) and every level is summed from those registers in pool_kernel's own order -- the window row
-// left to right, then the xor-shuffle tree over the window's rows -- so the three outputs are bit-identical to the three launches (tested).
+// left to right, then the xor-shuffle tree over the window's rows -- so the three outputs are bit-identical to the three launches
+// (tests/test_gpu_pool.py::test_pool3_equals_three_pools, through dffw_op_pool3).
 template <int PREC>
 __global__ __launch_bounds__(256) void pool3_kernel(const uint16_t *__restrict__ x, uint16_t *__restrict__ o2, uint16_t *__restrict__ o4, uint16_t *__restrict__ o8,
                                                     int B, int N, int H, int W, int C) {

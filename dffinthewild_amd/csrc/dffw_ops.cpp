@@ -227,6 +227,23 @@ int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int
     });
 }
 
+int dffw_op_pool3(int device, int precision, const float *x, int B, int C, int N, int H, int W, float *p2, float *p4, float *p8, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    if (!x || !p2 || !p4 || !p8) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (B < 1 || C < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape");
+    if (C % 8 || H % 8 || W % 8) return fail(DFFW_EINVAL, "the pyramid's pools need C, H and W multiples of 8, got C %d, %dx%d", C, H, W);
+    HIPCHK(hipSetDevice(device));
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, true, [&](Run &r) {
+        Act in = stage_in(r, x, B, C, N, H, W), a2, a4, a8;
+        r.pool3(in, a2, a4, a8);
+        stage_out(r, a2, p2);
+        stage_out(r, a4, p4);
+        stage_out(r, a8, p8);
+    });
+}
+
 // ---- block entry points: one SRD / EFD block of the front end, one feature block of the alignment network, through the graph's own
 // srd() / efd() / of_block().  The block's convs are packed under the keys the graph looks up, so the dispatch is the forward's itself.
 int dffw_op_srd(int device, int precision, const float *x, int B, int C, int N, int H, int W, const float *w0, const float *bn0,

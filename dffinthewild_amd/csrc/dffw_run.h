@@ -555,6 +555,18 @@ struct Run {
         }
         return out;
     }
+    // the three average pools (1,2,2), (1,4,4), (1,8,8) of x in one pass (pool3_kernel; H and W multiples of 8): the pyramid's and dffw_op_pool3's one launch
+    void pool3(const Act &x, Act &p2, Act &p4, Act &p8) {
+        p2 = act(x.B, x.N, x.H / 2, x.W / 2, x.C);
+        p4 = act(x.B, x.N, x.H / 4, x.W / 4, x.C);
+        p8 = act(x.B, x.N, x.H / 8, x.W / 8, x.C);
+        if (ok() && !dry) {
+            char kn[48];
+            snprintf(kn, sizeof kn, "dffw::pool3_kernel<%d>", e->prec);
+            launch_unnamed(kn, "avgpool (1,2,2)+(1,4,4)+(1,8,8)", "", 0.0, (double)(x.pixels() + p2.pixels() + p4.pixels() + p8.pixels()) * x.C * elem_bytes(), "pool3", 0,
+                           [&](unsigned long long *) { return launch_pool3(e->prec, x.p, p2.p, p4.p, p8.p, x.B, x.N, x.H, x.W, x.C, s); });
+        }
+    }
 
     void tap(const char *name, const Act &a) {
         if (!ok() || dry) return;

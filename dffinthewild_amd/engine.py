@@ -94,6 +94,7 @@ def _load():
                                       POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
                                       POINTER(c_float), POINTER(c_float), c_void_p, c_int, c_void_p, c_void_p, POINTER(c_float), c_void_p, c_void_p]
     lib.dffw_op_pool.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.dffw_op_pool3.argtypes = [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 4
     lib.dffw_op_srd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 6 + [c_void_p] * 3
     lib.dffw_op_efd.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int] + [POINTER(c_float)] * 4 + [c_int, c_void_p, c_void_p]
     lib.dffw_op_of_block.argtypes = [c_int, c_int, c_void_p] + [c_int] * 7 + [POINTER(c_float)] * 5 + [c_void_p] * 2
@@ -194,7 +195,7 @@ AUG_NPARAMS = 8     # DFFW_AUG_NPARAMS: crop row, crop col, contrast, brightness
 ABI_SYMBOLS = (
     "dffw_version", "dffw_last_error", "dffw_param_count", "dffw_param_info", "dffw_engine_create",
     "dffw_engine_destroy", "dffw_engine_precision", "dffw_workspace_bytes", "dffw_forward",
-    "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_regress",
+    "dffw_forward_taps", "dffw_profile_enable", "dffw_profile_collect", "dffw_op_conv3d", "dffw_op_conv3d_ex", "dffw_op_pool", "dffw_op_pool3", "dffw_op_regress",
     "dffw_op_regress_heads",
     "dffw_op_fov_warp", "dffw_forward_e2e", "dffw_last_conv_kernel", "dffw_op_srd", "dffw_op_efd", "dffw_last_op_kernels",
     "dffw_op_of_block", "dffw_op_head_tail", "dffw_op_head_front",
@@ -984,7 +985,7 @@ def op_head_front(fe, w0, bn0, alpha, fov, *, precision="bf16x3", out=None):
 
 
 def op_kernels():
-    """Kernel names of every launch of this thread's last op_srd / op_efd / op_of_block / op_head_front / op_head_tail / op_regress_heads / op_heads_backward
+    """Kernel names of every launch of this thread's last op_pool3 / op_srd / op_efd / op_of_block / op_head_front / op_head_tail / op_regress_heads / op_heads_backward
     call, in launch order."""
     s = lib.dffw_last_op_kernels().decode()
     return s.split(";") if s else []
@@ -998,6 +999,18 @@ def op_pool(x, k, mode="max", precision="bf16x3"):
     with torch.cuda.device(dev):
         _check(lib.dffw_op_pool(dev, PRECISIONS[precision], 0 if mode == "max" else 1, k, _ptr(x), B, C, N, H, W, _ptr(y), _stream_ptr(dev)), "dffw_op_pool")
     return y
+
+
+def op_pool3(x, precision="bf16x3"):
+    """(p2, p4, p8): the average pools (1,2,2), (1,4,4), (1,8,8) of x (B,C,N,H,W) float32 CUDA, C, H and W multiples of 8, from one pass of the
+    forward's dffw::pool3_kernel (dffw_op_pool3; op_kernels() names it), each bit-identical to op_pool(x, k, "avg")."""
+    B, C, N, H, W = x.shape
+    x = x.contiguous()
+    ps = [torch.empty((B, C, N, H // k, W // k), dtype=torch.float32, device=x.device) for k in (2, 4, 8)]
+    dev = _dev(x)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_pool3(dev, PRECISIONS[precision], _ptr(x), B, C, N, H, W, *[_ptr(p) for p in ps], _stream_ptr(dev)), "dffw_op_pool3")
+    return tuple(ps)
 
 
 def op_regress(score, focus_dists, H, W):

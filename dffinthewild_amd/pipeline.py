@@ -600,8 +600,8 @@ class AvgPool3d(torch.autograd.Function):
 
 
 class AvgPoolPyramid(torch.autograd.Function):
-    """p2, p4, p8 = AvgPoolPyramid.apply(x, precision): the average pools (1,2,2), (1,4,4), (1,8,8) of one volume (three engine.op_pool calls,
-    bit-identical to the forward's single pass); the backward is ONE engine.op_pool3_backward, an output without a gradient counting as zeros."""
+    """p2, p4, p8 = AvgPoolPyramid.apply(x, precision): the average pools (1,2,2), (1,4,4), (1,8,8) of one volume (one engine.op_pool3, the
+    forward's single pass, bit-identical to three engine.op_pool calls); the backward is ONE engine.op_pool3_backward, an output without a gradient counting as zeros."""
 
     @staticmethod
     def forward(ctx, x, precision="bf16x3"):
@@ -609,7 +609,7 @@ class AvgPoolPyramid(torch.autograd.Function):
         x = x.detach().float()
         ctx.precision = precision
         ctx.set_materialize_grads(False)     # backward fills in the zeros itself, at the shapes it derives
-        return tuple(engine.op_pool(x, k, "avg", precision) for k in (2, 4, 8))
+        return engine.op_pool3(x, precision)
 
     @staticmethod
     def backward(ctx, g2, g4, g8):

@@ -182,6 +182,13 @@ int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin,
 int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int B, int C, int N,
                  int H, int W, float *y, void *hip_stream);
 
+/* The pyramid's three average pools (1,2,2), (1,4,4), (1,8,8) of one volume (hourglassup.forward, DEN.py:212-216) in one pass, by the forward's own
+ * dffw::pool3_kernel<precision> (dffw_last_op_kernels names it): p2 (B,C,N,H/2,W/2), p4 (B,C,N,H/4,W/4), p8 (B,C,N,H/8,W/8), device fp32, each
+ * bit-identical to dffw_op_pool(mode 1, k).  Test-only; allocates, poisons its workspace with 0xFF and synchronises.  C, H or W no multiple
+ * of 8 is DFFW_EINVAL. */
+int dffw_op_pool3(int device, int precision, const float *x, int B, int C, int N, int H, int W, float *p2, float *p4, float *p8,
+                  void *hip_stream);
+
 /* One SRD block of the front end (DEN.py:317-330: feat = relu(x + BN(conv(relu(BN(conv(x)))))), y = feat +
  * relu(conv1x1x1(relu(conv3x1x1(feat))))) through the forward's own dispatch, C = 8, 16 or 32 (FM_measure.Focus_extraction.2,
  * FM_conv1.1, FM_conv2.1).  Test-only.  x, y: device fp32 (B,C,N,H,W).  w0, w2: host fp32 (C,C,1,3,3) with bn0, bn2 (4*C

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from dffinthewild_amd import graph, synth
 from oracle import error_bounds as eb
@@ -128,10 +129,13 @@ def test_srd_block_every_path(eng, shape, C, prec, monkeypatch):
         match_kernels(ks, want, eng.PRECISIONS[prec])
         bounded(y, r, prec, ks, "SRD %d %s y" % (C, name))
         bounded(pooled, rp, prec, ks, "SRD %d %s pooled" % (C, name))
+        # y is the stored value (hi + lo is exact in fp32) and the split is monotone: the pooled copy is max_pool(y) bit for bit on every path
+        assert torch.equal(pooled, F.max_pool3d(y, (1, 2, 2))), "SRD %d %s: pooled copy is not max_pool(y)" % (C, name)
         if first is None:
             first = (y.cpu(), pooled.cpu())
             y2, p2 = eng.op_srd(xd, *wts, pooled=True, precision=prec)
             assert torch.equal(y2, y) and torch.equal(p2, pooled), "repeated call differs"
+            assert torch.equal(p2, F.max_pool3d(y2, (1, 2, 2)))
         else:
             eb.check_pair(y.cpu(), first[0], r, prec, "SRD %d %s vs fused" % (C, name))
             eb.check_pair(pooled.cpu(), first[1], rp, prec, "SRD %d %s pooled vs fused" % (C, name))
@@ -150,6 +154,7 @@ def test_srd_block_at_the_forward_threshold(eng, C, B, N, H, W, monkeypatch):
     assert ks == ["dffw::srd_roll%s_kernel<0, true>" % ("16" if C == 16 else "")], ks
     bounded(y, r, "bf16x3", ks, "SRD %d y" % C)
     bounded(pooled, rp, "bf16x3", ks, "SRD %d pooled" % C)
+    assert torch.equal(pooled, F.max_pool3d(y, (1, 2, 2))), "SRD %d: pooled copy is not max_pool(y)" % C
 
 
 # ---- SRD, 32 channels -----------------------------------------------------------------------------------------------------------
@@ -171,6 +176,8 @@ def test_srd32_block_every_path(eng, B, N, H, W, prec, monkeypatch):
         assert len(ks) == 4 and not any("srd_" in k for k in ks), ks
     bounded(y, r, prec, ks, "SRD 32 y")
     assert torch.equal(eng.op_srd(xd, *wts, precision=prec), y), "repeated call differs"
+    yp, pooled = eng.op_srd(xd, *wts, pooled=True, precision=prec)
+    assert torch.equal(pooled, F.max_pool3d(yp, (1, 2, 2))), ("SRD 32: pooled copy is not max_pool(y)", eng.op_kernels())
     if W % 16 == 0:
         monkeypatch.setenv("DFFW_NO_FUSED_ATTENTION", "1")
         y2 = eng.op_srd(xd, *wts, precision=prec)
@@ -280,6 +287,8 @@ def test_blocks_match_the_forward_taps(eng, which, min_units, monkeypatch):
                bn(p + ".Focus_Measure.conv.2.1"), w(p + ".N_ch_attention.0.weight"), w(p + ".N_ch_attention.2.weight"))
         r, _ = eb.srd_ref64(taps[src].cpu(), *wts, "bf16x3")
         y = eng.op_srd(taps[src], *wts, pooled=C < 32)
+        if C < 32:
+            assert torch.equal(y[1], F.max_pool3d(y[0], (1, 2, 2))), "SRD %d at %s: pooled copy is not max_pool(y)" % (C, which)
         y = y[0] if C < 32 else y
         ks = eng.op_kernels()
         fwd = _layer_kernels(prof, p)

@@ -759,7 +759,7 @@ def test_conv_epilogue_variants(eng):
         bounded(got, eb.conv_ref64(x, w, residual=res, relu=relu), "bf16x3", eng.last_conv_kernel(), "relu=%d" % relu)
 
 
-@pytest.mark.parametrize("prec", ["bf16x3", "fp16"])
+@pytest.mark.parametrize("prec", ["bf16x3", "fp16", "bf16"])
 def test_pools(eng, prec):
     x = rnd(2, 32, 3, 16, 32, seed=11)
     assert rel(eng.op_pool(x.cuda(), 2, "max", prec), F.max_pool3d(x, (1, 2, 2), (1, 2, 2))) <= TOL[prec]

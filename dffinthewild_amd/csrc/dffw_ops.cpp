@@ -214,6 +214,34 @@ int dffw_op_conv3d_ex(int device, int precision, const float *x, int B, int Cin,
     });
 }
 
+// The forward 3x3x3 stride-1 conv over the virtual concatenation [xa | xb] (ConvOpt::in1), as the hourglass conv0 layers and the pyramid's
+// combine1 / combine2 run it: one layer of Ca + Cb input channels (pack_conv sees only the total), each tensor staged into records of its own,
+// through the same Run::conv path the graph uses; dffw_last_op_kernels() is not this op's to set
+int dffw_op_conv3d_cat(int device, int precision, const float *xa, int Ca, const float *xb, int Cb, int B, int N, int H, int W, const float *weight,
+                       int Cout, const float *bn, const float *conv_bias, const float *residual, int relu, float *y, void *hip_stream) {
+    if (!xa || !xb || !weight || !y) return fail(DFFW_EINVAL, "null argument");
+    if (precision < 0 || precision > 2) return fail(DFFW_EINVAL, "unknown precision %d", precision);
+    if (B < 1 || N < 1 || H < 1 || W < 1) return fail(DFFW_EINVAL, "bad shape B=%d N=%d H=%d W=%d", B, N, H, W);
+    if (Ca < 8 || Cb < 8 || Ca % 8 || Cb % 8 || (int64_t)Ca + Cb > 192)
+        return fail(DFFW_EINVAL, "Ca and Cb must be multiples of 8 from 8 on with Ca + Cb <= 192, got %d and %d", Ca, Cb);
+    if (Cout < 8 || Cout % 8 || Cout > 128) return fail(DFFW_EINVAL, "Cout must be a multiple of 8 from 8 to 128, got %d", Cout);
+    HIPCHK(hipSetDevice(device));
+    LayerDef L{"op", "", Ca + Cb, Cout, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1, false, true, false};
+    OpEngine eng(device, precision);
+    if (int rc = pack_conv(L, precision, weight, bn, conv_bias, eng.convs["op"])) return rc;
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act a = stage_in(r, xa, B, Ca, N, H, W), b = stage_in(r, xb, B, Cb, N, H, W), res;
+        ConvOpt o;
+        o.relu = relu;
+        o.in1 = &b;
+        if (residual) {
+            res = stage_in(r, residual, B, Cout, N, H, W);
+            o.res0 = &res;
+        }
+        stage_out(r, r.conv("op", a, o), y);
+    });
+}
+
 int dffw_op_pool(int device, int precision, int mode, int k, const float *x, int B, int C, int N, int H, int W, float *y,
                  void *hip_stream) {
     if (!x || !y) return fail(DFFW_EINVAL, "null argument");

@@ -150,6 +150,8 @@ def _load():
     lib.dffw_conv_cat_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_conv_cat_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]
     lib.dffw_op_conv_cat_backward.argtypes = [c_int, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [POINTER(c_float), c_int] + [c_void_p] * 5
+    lib.dffw_op_conv3d_cat.argtypes = [c_int, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [POINTER(c_float), c_int, POINTER(c_float), POINTER(c_float),
+                                                                                                     c_void_p, c_int, c_void_p, c_void_p]
     c_double = ctypes.c_double
     lib.dffw_bn_train_workspace_bytes.argtypes = [c_int] * 5
     lib.dffw_bn_train_workspace_bytes.restype = c_int64
@@ -211,7 +213,7 @@ ABI_SYMBOLS = (
     "dffw_stem_wgrad_workspace_bytes", "dffw_stem_wgrad", "dffw_op_stem_backward",
     "dffw_score_conv_dgrad", "dffw_score_conv_wgrad_workspace_bytes", "dffw_score_conv_wgrad", "dffw_op_score_conv_backward",
     "dffw_adam_tensors_per_launch", "dffw_adam_step",
-    "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward",
+    "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward", "dffw_op_conv3d_cat",
     "dffw_heads_backward",
     "dffw_engine_update", "dffw_engine_repack_stats", "dffw_engine_packed_bytes", "dffw_engine_packed_read",
 )
@@ -638,6 +640,44 @@ def op_conv_cat_backward(xa, xb, weight, grad_y, *, precision="bf16x3", need=("x
         _check(lib.dffw_op_conv_cat_backward(dev, PRECISIONS[precision], _ptr(xa), Ca, _ptr(xb), Cb, B, N, H, W, _f32(w), Cout, _ptr(grad_y), _ptr(gxa),
                                              _ptr(gxb), _ptr(gw), _stream_ptr(dev)), "dffw_op_conv_cat_backward")
     return gxa, gxb, gw
+
+
+def op_conv3d_cat(xa, xb, weight, *, bn=None, bias=None, residual=None, relu=0, precision="bf16x3"):
+    """y = [relu](BN(conv3d(cat([xa, xb], 1), weight)) [+ residual]) with the concatenation left virtual (dffw_op_conv3d_cat, DESIGN.md section
+    26): kernel (3,3,3), stride 1, pad 1; ``xa`` (B,Ca,N,H,W), ``xb`` (B,Cb,N,H,W) and ``residual`` (B,Cout,N,H,W) float32 on the GPU, ``weight``
+    CPU/GPU float32 (Cout,Ca+Cb,3,3,3); ``bn``, ``bias`` and ``relu`` as op_conv3d takes them.  The forward's dispatch picks the kernel, whose
+    fill reads the two tensors; last_conv_kernel() names it.  The channel counts' limits are the library's to refuse."""
+    name = "op_conv3d_cat"
+    checks = (lambda: any(t.dim() != 5 for t in (xa, xb, weight)) and "xa, xb and weight must have 5 dimensions",
+              lambda: (xa.shape[0], *xa.shape[2:]) != (xb.shape[0], *xb.shape[2:]) and
+              f"xa {tuple(xa.shape)} and xb {tuple(xb.shape)} differ outside the channel axis",
+              lambda: tuple(weight.shape[2:]) != (3, 3, 3) and f"the conv over a concatenation is 3x3x3 stride 1 pad 1, got a {tuple(weight.shape[2:])} kernel",
+              lambda: weight.shape[1] != xa.shape[1] + xb.shape[1] and
+              f"weight {tuple(weight.shape)} does not take {xa.shape[1]} + {xb.shape[1]} input channels",
+              lambda: residual is not None and tuple(residual.shape) != (xa.shape[0], weight.shape[0], *xa.shape[2:]) and
+              f"residual {tuple(residual.shape)} is not the conv's output shape {(xa.shape[0], weight.shape[0], *xa.shape[2:])}")
+    for check in checks:
+        msg = check()
+        if msg:
+            raise ValueError(f"{name}: {msg}")
+    tensors = [t for t in (xa, xb, residual) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise DffwError(f"{name} needs GPU tensors (no CPU fallback)")
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{name}: xa, xb and residual must be on one GPU")
+    w = _host_f32(weight)
+    xa, xb = (t.detach().float().contiguous() for t in (xa, xb))
+    res = residual.detach().float().contiguous() if residual is not None else None
+    bnh = _bn_host(bn) if bn is not None else None
+    bh = _host_f32(bias) if bias is not None else None
+    dev = _dev(xa)
+    B, Ca, N, H, W = xa.shape
+    Cb, Cout = xb.shape[1], w.shape[0]
+    y = torch.empty((B, Cout, N, H, W), dtype=torch.float32, device=xa.device)
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_conv3d_cat(dev, PRECISIONS[precision], _ptr(xa), Ca, _ptr(xb), Cb, B, N, H, W, _f32(w), Cout, _f32(bnh) if bnh is not None else None,
+                                      _f32(bh) if bh is not None else None, _ptr(res), relu, _ptr(y), _stream_ptr(dev)), "dffw_op_conv3d_cat")
+    return y
 
 
 def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):

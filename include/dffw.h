@@ -608,6 +608,19 @@ int dffw_conv_cat_wgrad(int device, int precision, const void *xa, int Ca, const
 int dffw_op_conv_cat_backward(int device, int precision, const float *xa, int Ca, const float *xb, int Cb, int B, int N, int H, int W,
                               const float *weight, int Cout, const float *grad_y, float *grad_xa, float *grad_xb, float *grad_w, void *hip_stream);
 
+/* dffw_op_conv3d_cat: the FORWARD conv over the same virtual concatenation, one operator for the kernel tests (tests/test_gpu_conv_cat.py,
+ * DESIGN.md §26): y = [relu](BN(conv3d(cat([xa, xb], 1), weight)) [+ residual]), kernel (3,3,3), stride 1, pad 1, not transposed -- the
+ * geometry of the five layers whose input is two tensors (the hourglass conv0 layers, the pyramid's combine1 / combine2).  xa (B,Ca,N,H,W),
+ * xb (B,Cb,N,H,W), residual (B,Cout,N,H,W) or NULL and y (B,Cout,N,H,W) device fp32; weight host fp32 (Cout, Ca + Cb, 3,3,3); bn, conv_bias,
+ * relu as dffw_op_conv3d takes them.  One layer of Ca + Cb input channels is packed, each tensor is staged into activation records of its
+ * own and the conv runs through the forward's own dispatch with the second tensor as ConvOpt::in1: the kernel choice, and the fill that reads
+ * two tensors, are the forward's.  The concatenation is never materialised.  dffw_last_conv_kernel() names the launch.  Allocates, poisons
+ * its workspace with 0xFF and synchronises.  DFFW_EINVAL with a message, before the GPU is touched: a null xa, xb, weight or y; a precision
+ * outside 0..2; B, N, H or W below 1; Ca or Cb below 8 or no multiple of 8; Ca + Cb > 192; Cout below 8, above 128 or no multiple of 8. */
+int dffw_op_conv3d_cat(int device, int precision, const float *xa, int Ca, const float *xb, int Cb, int B, int N, int H, int W,
+                       const float *weight, int Cout, const float *bn, const float *conv_bias, const float *residual, int relu, float *y,
+                       void *hip_stream);
+
 /* ---- synthetic focal stacks (Simulator/synthetic_blur_movement.py:155-280) ---------------------------------------------
  * Replaces the reference's per-image NumPy / OpenCV loop that made End_to_End's training data: for every sample b an RGB-D
  * frame at working size (H, W) and a camera, N slices focused at 1/linspace(1/max_focus, 1/min_focus, N); slice n >= 1 is

@@ -9,8 +9,8 @@ per sample (DFFW_ROLL_ZSPLIT=2: ranges that start and end inside the volume), th
 arithmetic, equal bit for bit).  The input is non-zero and carries a per-slice offset.  Held per element to the forward-error bound of
 oracle/error_bounds.py against F.conv3d / F.conv_transpose3d in float64.
 
-The two-source forms of conv_rollx (8 + 8 -> 8, 16 + 16 -> 16 over a virtual concat) have no single-operator entry point: they run in the
-forward tests (tests/test_gpu_forward.py)."""
+The two-source forms of these kernels (8 + 8 -> 8, 16 + 16 -> 16, ... over a virtual concat) run on the same slice stream, through
+engine.op_conv3d_cat, in tests/test_gpu_conv_cat.py."""
 import pytest
 import torch
 

@@ -4,11 +4,13 @@
 //   pw       3x1x1 pad (1,0,0) and 1x1x1: no in-plane taps                    DESIGN.md §15   dffw_conv_pw_wgrad.hip
 //   stem     Conv3d(3, 8, (1,9,9), pad (0,8,8), dilation (1,2,2))             DESIGN.md §17   dffw_stem_wgrad.hip
 //   score    Cin -> 1, 1x1x1 and 3x3x3 (and their data gradient)              DESIGN.md §19   dffw_score_grad.hip
+//   att      the attention tail, both convs and both masks, data gradient too DESIGN.md §27   dffw_att_grad.hip
 // A family owns its geometry recogniser and its plan_*(): geometry -> shape (check_volume) -> the kernel's arguments, the grid and the workspace
 // size.  Its *_backward_check (for dffw_ops.cpp), its *_workspace_bytes and its record form all read that one Plan; a record form then checks its
 // pointers and ends in launch_record().  Every refusal comes in the order geometry, shape, null, alignment, workspace.  The record forms enqueue
 // on the caller's stream and allocate nothing.  The data gradient of the plain, pw and stem families is no kernel of its own: it is the adjoint
 // conv through the forward's dispatch (dffw_ops.cpp), and the stem has none.
+#include "dffw_att_grad.h"
 #include "dffw_conv_pw_wgrad.h"
 #include "dffw_conv_wgrad.h"
 #include "dffw_run.h"
@@ -249,8 +251,34 @@ Plan<ScoreArgs> plan_score(int precision, int B, int Cin, int N, int H, int W, c
     return p;
 }
 
+// ---- att --------------------------------------------------------------------------------------------------------------------------------------
+Plan<AttGradArgs> plan_att(int precision, int B, int C, int N, int H, int W) {
+    Plan<AttGradArgs> p{};
+    if (C != 8 && C != 16 && C != 32) {
+        p.rc = fail(DFFW_EINVAL, "the attention tails have 8, 16 or 32 channels, got %d", C);
+        return p;
+    }
+    // two counts are ints in the kernel: the plane rounded up to whole chunks, and the units B * chunks
+    const int64_t HW = (int64_t)H * W, chunks = (HW + attgrad::P - 1) / attgrad::P;
+    p.rc = check_volume("the attention tail backward", precision, B, N, H, W, {C}, 1, std::max(HW + attgrad::P, B * chunks), "pixels of a plane or units");
+    if (p.rc) return p;
+    const Switches sw = Switches::read();
+    AttGradArgs &a = p.a;
+    a.B = B;
+    a.N = N;
+    a.HW = H * W;
+    a.chunks = (int)chunks;
+    a.total_units = B * a.chunks;
+    a.flush_steps = std::min(sw.attgrad_flush_steps, attgrad::FLUSH_STEPS);
+    p.sub = C;
+    p.grid_x = att_tail_bwd_grid_x(a, sw.attgrad_wgs);
+    p.bytes = (int64_t)p.grid_x * attgrad::block(C) * (int64_t)sizeof(double);
+    return p;
+}
+
 }  // namespace
 
+int dffw::att_tail_backward_check(int precision, int B, int C, int N, int H, int W) { return plan_att(precision, B, C, N, H, W).rc; }
 int dffw::conv_backward_check(int precision, int B, int Cin, int N, int H, int W, int Cout, const int kernel[3], const int stride[3], const int pad[3],
                               int transposed) {
     return plan_conv(precision, nullptr, B, Cin, N, H, W, nullptr, Cout, kernel, stride, pad, transposed).rc;
@@ -315,6 +343,39 @@ int dffw_conv_pw_wgrad(int device, int precision, const void *x, int B, int Cin,
     p.a.partial = (double *)workspace;
     return launch_record("wgrad", p.bytes, workspace_bytes, device, conv_pw_wgrad_kernel_name(precision, p.sub), "dffw::conv_pw_wgrad_finish_kernel",
                          [&] { return launch_conv_pw_wgrad(precision, p.sub, p.a, p.grid_x, grad_w, (hipStream_t)hip_stream); });
+}
+
+int64_t dffw_att_tail_backward_workspace_bytes(int B, int C, int N, int H, int W) { return plan_att(0, B, C, N, H, W).bytes; }
+
+int dffw_att_tail_backward(int device, int precision, const void *x, const void *a, const void *t, const void *grad_y, int B, int C, int N, int H, int W,
+                           const float *w3, const float *w1, void *grad_x, float *grad_w3, float *grad_w1, void *workspace, int64_t workspace_bytes,
+                           void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    Plan<AttGradArgs> p = plan_att(precision, B, C, N, H, W);
+    if (p.rc) return p.rc;
+    if ((grad_w3 != nullptr) != (grad_w1 != nullptr)) return fail(DFFW_EINVAL, "grad_w3 and grad_w1 go together");
+    if (!grad_x && !grad_w3) return DFFW_OK;   // no output: nothing to launch
+    if (!x || !a || !t || !grad_y || !w1 || (grad_x && !w3) || (grad_w3 && !workspace)) return fail(DFFW_EINVAL, "null argument");
+    if (!aligned(x, 16) || !aligned(a, 16) || !aligned(t, 16) || !aligned(grad_y, 16) || !aligned(grad_x, 16) || !aligned(workspace, 8))
+        return fail(DFFW_EINVAL, "records must be 16-byte aligned");
+    if (!aligned(w3, 4) || !aligned(w1, 4) || !aligned(grad_w3, 4) || !aligned(grad_w1, 4)) return fail(DFFW_EINVAL, "the filters and their gradients must be 4-byte aligned");
+    p.a.x = (const uint16_t *)x;
+    p.a.a = (const uint16_t *)a;
+    p.a.t = (const uint16_t *)t;
+    p.a.gy = (const uint16_t *)grad_y;
+    p.a.gx = (uint16_t *)grad_x;
+    p.a.w3 = w3;
+    p.a.w1 = w1;
+    p.a.partial = grad_w3 ? (double *)workspace : nullptr;
+    const char *kernel = att_tail_bwd_kernel_name(precision, C);
+    if (!grad_w3) {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(launch_att_tail_bwd(precision, C, p.a, p.grid_x, nullptr, nullptr, (hipStream_t)hip_stream));
+        dffw_set_last_op_kernels(kernel);
+        return DFFW_OK;
+    }
+    return launch_record("attention tail backward", p.bytes, workspace_bytes, device, kernel, "dffw::att_tail_bwd_finish_kernel",
+                         [&] { return launch_att_tail_bwd(precision, C, p.a, p.grid_x, grad_w3, grad_w1, (hipStream_t)hip_stream); });
 }
 
 int64_t dffw_stem_wgrad_workspace_bytes(int B, int N, int H, int W) { return plan_stem(0, nullptr, nullptr, B, N, H, W).bytes; }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "dffw_bn.h"
+#include "dffw_att_grad.h"
 #include "dffw_conv_pw_wgrad.h"
 #include "dffw_conv_wgrad.h"
 #include "dffw_pool_grad.h"
@@ -626,6 +627,34 @@ int dffw_op_grad_combine(int device, int precision, const float *a, const float 
         Act oa = r.act(B, N, H, W, C);
         if (real(r)) r.err = dffw_grad_combine(device, precision, aa.p, ya.p, ba.p, B, C, N, H, W, oa.p, r.s);
         stage_out(r, oa, out);
+    });
+}
+
+// ---- backward of the attention tail as one node: w3 and w1 are host fp32 and go to the device as they are
+int dffw_op_att_tail_backward(int device, int precision, const float *x, const float *a, const float *t, const float *grad_y, int B, int C, int N, int H,
+                              int W, const float *w3, const float *w1, float *grad_x, float *grad_w3, float *grad_w1, void *hip_stream) {
+    dffw_set_last_op_kernels("");
+    // the record form's refusals first: nothing is staged for a call it will not take
+    if (int rc = att_tail_backward_check(precision, B, C, N, H, W)) return rc;
+    if ((grad_w3 != nullptr) != (grad_w1 != nullptr)) return fail(DFFW_EINVAL, "grad_w3 and grad_w1 go together");
+    if (!grad_x && !grad_w3) return DFFW_OK;
+    if (!x || !a || !t || !grad_y || !w1 || (grad_x && !w3)) return fail(DFFW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(device));
+    const int64_t wsb = grad_w3 ? dffw_att_tail_backward_workspace_bytes(B, C, N, H, W) : 0;
+    const int64_t n1 = (int64_t)C * C, n3 = 3 * n1;
+    OpEngine eng(device, precision);
+    return run_op(eng, (hipStream_t)hip_stream, false, [&](Run &r) {
+        Act xa = stage_in(r, x, B, C, N, H, W), aa = stage_in(r, a, B, C, N, H, W), ta = stage_in(r, t, B, C, N, H, W), ga = stage_in(r, grad_y, B, C, N, H, W);
+        Act gx = grad_x ? r.act(B, N, H, W, C) : Act();
+        float *w1d = (float *)r.raw(n1 * sizeof(float)), *w3d = w3 ? (float *)r.raw(n3 * sizeof(float)) : nullptr;
+        void *ws = wsb ? r.raw(wsb) : nullptr;
+        if (real(r)) {
+            r.check(hipMemcpyAsync(w1d, w1, n1 * sizeof(float), hipMemcpyHostToDevice, r.s), "copy");
+            if (w3d && r.ok()) r.check(hipMemcpyAsync(w3d, w3, n3 * sizeof(float), hipMemcpyHostToDevice, r.s), "copy");
+            if (r.ok())
+                r.err = dffw_att_tail_backward(device, precision, xa.p, aa.p, ta.p, ga.p, B, C, N, H, W, w3d, w1d, gx.p, grad_w3, grad_w1, ws, wsb, r.s);
+        }
+        if (grad_x) stage_out(r, gx, grad_x);
     });
 }
 

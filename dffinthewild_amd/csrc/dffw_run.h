@@ -208,6 +208,9 @@ enum SwitchId {
        accumulator each) between two flushes, which can only be shortened (above 512: 512) */                                                             \
     X(PWGRAD_WGS, pwgrad_wgs, 8, 0)                                                                                                                        \
     X(PWGRAD_FLUSH_STEPS, pwgrad_flush_steps, 1, 512)                                                                                                      \
+    /* ... and of the attention tail's fused backward: workgroups of the launch, steps between two flushes (above 512: 512) */              \
+    X(ATTGRAD_WGS, attgrad_wgs, 8, 0)                                                                                                                      \
+    X(ATTGRAD_FLUSH_STEPS, attgrad_flush_steps, 1, 512)                                                                                                    \
     /* train-mode BatchNorm: workgroups of each of its streaming launches (0: its default; below 8: 8, one per XCD).  Changes only the     \
        order of the float64 additions */                                                                                                                   \
     X(BN_WGS, bn_wgs, 1, 0)                                                                                                                                \

@@ -167,6 +167,10 @@ def _load():
     lib.dffw_conv_pw_wgrad_workspace_bytes.restype = c_int64
     lib.dffw_conv_pw_wgrad.argtypes = [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                        POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_int64, c_void_p]
+    lib.dffw_att_tail_backward_workspace_bytes.argtypes = [c_int] * 5
+    lib.dffw_att_tail_backward_workspace_bytes.restype = c_int64
+    lib.dffw_att_tail_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 6 + [c_int64, c_void_p]
+    lib.dffw_op_att_tail_backward.argtypes = [c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [POINTER(c_float)] * 2 + [c_void_p] * 4
     lib.dffw_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
     lib.dffw_op_grad_combine.argtypes = [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
     lib.dffw_pool_backward.argtypes = [c_int] * 4 + [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
@@ -215,6 +219,7 @@ ABI_SYMBOLS = (
     "dffw_adam_tensors_per_launch", "dffw_adam_step",
     "dffw_conv_cat_wgrad_workspace_bytes", "dffw_conv_cat_wgrad", "dffw_op_conv_cat_backward", "dffw_op_conv3d_cat",
     "dffw_heads_backward",
+    "dffw_att_tail_backward_workspace_bytes", "dffw_att_tail_backward", "dffw_op_att_tail_backward",
     "dffw_engine_update", "dffw_engine_repack_stats", "dffw_engine_packed_bytes", "dffw_engine_packed_read",
 )
 
@@ -699,6 +704,43 @@ def op_grad_combine(a, y=None, b=None, *, precision="bf16x3"):
         _check(lib.dffw_op_grad_combine(dev, PRECISIONS[precision], _ptr(a), _ptr(y), _ptr(b), B, C, N, H, W, _ptr(out), _stream_ptr(dev)),
                "dffw_op_grad_combine")
     return out
+
+
+def op_attention_tail(x, w3, w1, *, precision="bf16x3"):
+    """The attention tail of a Feature_Extraction block, ``y = x + relu(conv111(relu(conv311(x))))``, as the three steps
+    that define it: ``a = op_conv3d(x, w3, pad=(1,0,0), relu=1)``, ``t = op_conv3d(a, w1, relu=1)``, ``y = x + t`` in fp32.  Returns (y, a, t);
+    ``a`` and ``t`` are what op_attention_tail_backward reads its masks from."""
+    a = op_conv3d(x, w3, pad=(1, 0, 0), relu=1, precision=precision)
+    t = op_conv3d(a, w1, relu=1, precision=precision)
+    return x + t, a, t
+
+
+def op_attention_tail_backward(x, a, t, grad_y, w3, w1, *, precision="bf16x3", need=("x", "w")):
+    """(grad_x, grad_w3, grad_w1) of <grad_y, x + relu(conv111(relu(conv311(x))))> in one kernel (dffw_op_att_tail_backward).
+    ``x``, ``a``, ``t`` (op_attention_tail's) and ``grad_y`` (B,C,N,H,W) float32 on the GPU, C = 8, 16 or 32; ``w3`` (C,C,3,1,1) and ``w1``
+    (C,C,1,1,1) CPU/GPU float32.  The ReLU masks are those of the stored ``a`` and ``t``.  ``need``: which of "x", "w" to compute ("w": both
+    weight gradients); the other entries are None."""
+    name = "op_attention_tail_backward"
+    tensors = (x, a, t, grad_y)
+    if any(v.device.type != "cuda" for v in tensors):
+        raise DffwError(f"{name} needs GPU tensors (no CPU fallback)")
+    if x.dim() != 5 or any(v.shape != x.shape for v in tensors):
+        raise ValueError(f"{name}: x, a, t and grad_y must be 5-dimensional tensors of one shape")
+    B, C, N, H, W = x.shape
+    if tuple(w3.shape) != (C, C, 3, 1, 1) or tuple(w1.shape) != (C, C, 1, 1, 1):
+        raise ValueError(f"{name}: w3 {tuple(w3.shape)} and w1 {tuple(w1.shape)} are not ({C},{C},3,1,1) and ({C},{C},1,1,1)")
+    if set(need) - {"x", "w"}:
+        raise ValueError(f"{name}: need {tuple(need)} names something other than 'x', 'w'")
+    x, a, t, grad_y = (v.detach().float().contiguous() for v in tensors)
+    w3h, w1h = _host_f32(w3), _host_f32(w1)
+    dev = _dev(x)
+    gx = torch.empty_like(x) if "x" in need else None
+    gw3 = torch.empty((C, C, 3, 1, 1), dtype=torch.float32, device=x.device) if "w" in need else None
+    gw1 = torch.empty((C, C, 1, 1, 1), dtype=torch.float32, device=x.device) if "w" in need else None
+    with torch.cuda.device(dev):
+        _check(lib.dffw_op_att_tail_backward(dev, PRECISIONS[precision], _ptr(x), _ptr(a), _ptr(t), _ptr(grad_y), B, C, N, H, W, _f32(w3h), _f32(w1h),
+                                             _ptr(gx), _ptr(gw3), _ptr(gw1), _stream_ptr(dev)), "dffw_op_att_tail_backward")
+    return gx, gw3, gw1
 
 
 POOL_MODES = {"max": 0, "avg": 1}   # dffw_op_pool's and dffw_op_pool_backward's mode

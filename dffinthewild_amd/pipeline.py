@@ -565,6 +565,51 @@ def batch_norm3d(x, gamma, beta, running_mean=None, running_var=None, *, residua
     return BatchNorm3d.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, precision)
 
 
+# ---- the attention tail: y = x + relu(conv111(relu(conv311(x)))) as ONE autograd node with one backward kernel -----------
+class AttentionTail(torch.autograd.Function):
+    """y = AttentionTail.apply(x, w3, w1, precision): engine.op_attention_tail (two forward convs and the skip add), keeping a and t; its backward
+    through engine.op_attention_tail_backward, one kernel for grad_x and both weight gradients, the ReLU masks read from the stored a and t."""
+
+    @staticmethod
+    def forward(ctx, x, w3, w1, precision="bf16x3"):
+        _dev(x, "x")
+        y, a, t = engine.op_attention_tail(x.detach().float(), w3, w1, precision=precision)
+        ctx.save_for_backward(x, a, t, w3, w1)
+        ctx.precision = precision
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, a, t, w3, w1 = ctx.saved_tensors
+        need = (("x",) if ctx.needs_input_grad[0] else ()) + (("w",) if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] else ())
+        gx, gw3, gw1 = engine.op_attention_tail_backward(x, a, t, grad_y, w3, w1, precision=ctx.precision, need=need)
+        return (gx, gw3.to(w3.device, w3.dtype) if ctx.needs_input_grad[1] else None, gw1.to(w1.device, w1.dtype) if ctx.needs_input_grad[2] else None,
+                None)
+
+
+def attention_tail(x, w3, w1, *, precision="bf16x3"):
+    """x + relu(conv111(relu(conv311(x)))) on the HIP kernels with gradients for x, w3 and w1: x (B,C,N,H,W) float32 CUDA with C = 8, 16 or 32,
+    w3 (C,C,3,1,1) and w1 (C,C,1,1,1) in PyTorch layout (CPU or CUDA), no bias.  The forward is bit for bit conv3d -> relu -> conv3d -> relu -> +."""
+    C = x.shape[1] if x.dim() == 5 else -1
+    if tuple(w3.shape) != (C, C, 3, 1, 1) or tuple(w1.shape) != (C, C, 1, 1, 1):
+        raise ValueError(f"attention_tail: x {tuple(x.shape)}, w3 {tuple(w3.shape)} and w1 {tuple(w1.shape)} are not (B,C,N,H,W), (C,C,3,1,1) and (C,C,1,1,1)")
+    return AttentionTail.apply(x, w3, w1, precision)
+
+
+def feature_extraction(x, params, *, precision="bf16x3", momentum=0.1):
+    """The Feature_Extraction block in training mode: conv 1x3x3 -> BN -> ReLU -> conv 1x3x3 -> BN -> + x -> ReLU -> attention tail, out of
+    conv3d, batch_norm3d and attention_tail.  ``params``: a mapping under the block's own key names -- Focus_Measure.conv.0.0.weight,
+    Focus_Measure.conv.0.1.{weight,bias,running_mean,running_var}, Focus_Measure.conv.2.0.weight, Focus_Measure.conv.2.1.*,
+    N_ch_attention.0.weight, N_ch_attention.2.weight -- i.e. a slice of a checkpoint or of a state_dict as it is.  The running statistics are
+    updated in place."""
+    def bn(v, key, **kw):
+        return batch_norm3d(v, params[key + ".weight"], params[key + ".bias"], params[key + ".running_mean"], params[key + ".running_var"],
+                            momentum=momentum, precision=precision, **kw)
+    h = bn(conv3d(x, params["Focus_Measure.conv.0.0.weight"], pad=(0, 1, 1), precision=precision), "Focus_Measure.conv.0.1", relu=True)
+    h = bn(conv3d(h, params["Focus_Measure.conv.2.0.weight"], pad=(0, 1, 1), precision=precision), "Focus_Measure.conv.2.1", residual=x, relu=True)
+    return attention_tail(h, params["N_ch_attention.0.weight"], params["N_ch_attention.2.weight"], precision=precision)
+
+
 # ---- the pools (DESIGN.md section 16): MaxPool3d((1,2,2)), AvgPool3d((1,k,k)) and the pyramid's three average pools as autograd nodes -----------
 class MaxPool3d(torch.autograd.Function):
     """y = MaxPool3d.apply(x, precision): the (1,2,2) max pool through engine.op_pool; the backward through engine.op_pool_backward sends each

@@ -489,6 +489,27 @@ int dffw_grad_combine(int device, int precision, const void *a, const void *y, c
 int dffw_op_grad_combine(int device, int precision, const float *a, const float *y, const float *b, int B, int C, int N, int H, int W,
                          float *out, void *hip_stream);
 
+/* ---- backward of the attention tail as one node ---------------------------------------------------------------------------
+ * y = x + relu(conv111(relu(conv311(x)))) with a = relu(conv311(x)) and t = relu(conv111(a)) kept by the forward; C is 8, 16 or 32, no bias.
+ *   gt = [t > 0] grad_y;  ga = [a > 0] W1^T gt;  grad_x = grad_y + the adjoint 3x1x1 conv of ga;  grad_w1 = sum gt a;  grad_w3 = sum ga x
+ * in ONE kernel, dffw::att_tail_bwd_kernel, that reads x, a, t and grad_y once and writes grad_x once (ga stays on chip, rounded to the record
+ * format), plus dffw::att_tail_bwd_finish_kernel for the weight gradients (dffw_last_op_kernels lists them): fp32 MFMA partials of at most 16 384
+ * pixels, added in float64 in a fixed order, no atomics -- two calls give identical bits.  The masks are those of the STORED a and t.
+ * dffw_att_tail_backward: enqueue-only on activation RECORDS (16-byte aligned), no allocation; w3 (C,C,3,1,1) and w1 (C,C,1,1,1) device fp32 in
+ * PyTorch layout (split by the kernel itself).  grad_x may be NULL, grad_w3 and grad_w1 may be NULL together (one without the other:
+ * DFFW_EINVAL); w3 may be NULL without grad_x (w1 is always read: ga needs it); a call with no output launches nothing.  grad_x may alias
+ * grad_y.  workspace: dffw_att_tail_backward_workspace_bytes(...) bytes, need not be cleared (0 for refused arguments; too short:
+ * DFFW_ENOMEM), and may be NULL without the weight gradients.  Refused with DFFW_EINVAL before the GPU is touched: C outside {8, 16, 32},
+ * dimensions < 1, 2^31 units (128-pixel columns) or more, an unknown precision.
+ * dffw_op_att_tail_backward: the same on device fp32 tensors (B,C,N,H,W) with HOST fp32 weights; allocates, poisons its workspace with 0xFF
+ * and synchronises. */
+int64_t dffw_att_tail_backward_workspace_bytes(int B, int C, int N, int H, int W);
+int dffw_att_tail_backward(int device, int precision, const void *x, const void *a, const void *t, const void *grad_y, int B, int C, int N, int H,
+                           int W, const float *w3, const float *w1, void *grad_x, float *grad_w3, float *grad_w1, void *workspace,
+                           int64_t workspace_bytes, void *hip_stream);
+int dffw_op_att_tail_backward(int device, int precision, const float *x, const float *a, const float *t, const float *grad_y, int B, int C, int N,
+                              int H, int W, const float *w3, const float *w1, float *grad_x, float *grad_w3, float *grad_w1, void *hip_stream);
+
 /* ---- backward of the pools ---------------------------------------------------------------------------------------------
  * The adjoints of MaxPool3d((1,2,2)) (the second branch of both res_stride_conv_3d blocks), of AvgPool3d((1,k,k)), k = 2, 4, 8, and of the
  * pyramid's three average pools of one volume (hourglassup) in one pass.  B, C, N, H, W describe the pools' INPUT, which is where the
